@@ -16,7 +16,10 @@
 //   * systematic rows are written from the ring image (no staging copy);
 //   * the compute waves issue no loads, so the compiler inserts no vmcnt waits for them: the
 //     loader waits for its DMA explicitly before the barrier that hands the plane over.
-// LDS: 2 x 23,552 B ring + 24 x 1,440 B staging = 81,664 B -> two workgroups (14 waves) per CU.
+// LDS: 2 x 23,040 B ring + 24 x 1,440 B staging + a 64 B mailbox = 80,704 B -> two workgroups (14
+// waves) per CU.  A launch may run on fewer workgroups than stripes (the stripe queue at the kernel).
+#include <atomic>
+#include <string.h>
 #include "kernels.hpp"
 #include "gf_dev.hpp"
 #include "dev_io.hpp"
@@ -38,7 +41,12 @@ constexpr uint32_t kSlotBytes = (kOwnBlk + kPartBlk) * 16;
 constexpr uint32_t kRing = 2;              // ring slots (planes in flight)
 constexpr uint32_t kStageBase = kRing * kSlotBytes;
 constexpr uint32_t kStageRows = 24;
-constexpr uint32_t kLdsBytes = kStageBase + kStageRows * RW;
+// the loader's hand-over of a task to the compute waves (stripe queue, below): eight dwords
+constexpr uint32_t kMailBase = kStageBase + kStageRows * RW;
+constexpr uint32_t kMailBytes = 64;
+enum : uint32_t { kMbJob = 0, kMbRows = 1, kMbWi = 2, kMbFix = 3, kMbEz = 4, kMbEx = 5 };
+constexpr uint32_t kNoTask = 0xffffffffu;
+constexpr uint32_t kLdsBytes = kMailBase + kMailBytes;
 static_assert(kLdsBytes <= 81920 - 1024, "two workgroups per CU, with a margin");
 constexpr int kOwnInstr = 10, kPartInstr = 13, kDmaInstr = kOwnInstr + kPartInstr;
 constexpr int kWaves = G + 1;              // six compute waves and a loader wave that issues every DMA
@@ -213,6 +221,37 @@ __device__ __forceinline__ void col1(const uint32_t *u1, uint32_t (&sl)[kSlots],
     for (int j = S + 1; j < kQ; j++) sl[kSl.slot[S][j]] = u1[j];
 }
 
+// What the loader wave holds of a task: where its DMA reads (everything but sl_lane is uniform).
+struct LTask {
+    u32x4 rs_src, rs_dst;
+    uint32_t src_al, sl_lane;  // sl_lane: lane i = byte offset of node i's slice in the destination
+    uint32_t zb, ze;           // planes [zb, ze), both even
+};
+
+// Persistent workgroups over a stripe queue.  A launch has a.ntasks tasks (kernels.hpp enc_task:
+// a stripe's ten rows of planes, or one part of them) and as many workgroups as the launcher chose;
+// a workgroup runs its block index as its first task and then draws queue positions gridDim.x +
+// atomicAdd(a.queue, 1) until they reach a.ntasks.  Nothing waits on another workgroup: no flag, no
+// spin, every loop bounded by the task count.
+//
+// The loader wave owns the queue.  During a task's first planes it draws the next position (lane
+// 0's atomicAdd), reads that task's descriptor and the one word at its data end, and leaves them
+// in the LDS mailbox (kMailBase) between B2 and B1 of the task's third plane; the compute waves
+// read the mailbox after B1 of the task's last plane, which also tells them whether there is a
+// next task.  After B1 of the last two planes the loader issues the NEXT task's first two planes
+// where planes ze and ze + 1 of this one would go -- the ring slot parity is unchanged because
+// every task's plane range starts and ends on an even plane -- so the compute waves go from one
+// task's last plane to the next one's first with the same two barriers per plane and no drain.
+//
+// Barrier count: loader and compute waves each pass one barrier before the first task (P: the
+// first mailbox and plane zb are in LDS) and then exactly two per plane of every task (B2, B1).
+// Both sides run the same task sequence: the compute waves take every task, and its end, from the
+// mailbox the loader wrote, and the first task always exists (gridDim.x <= a.ntasks).  A last task
+// with no successor differs only in that the loader issues nothing after B1 of its last two
+// planes; the barriers are the same.  Tasks have at least 10 planes, so the mailbox write at the
+// third plane comes after every compute wave read the previous mailbox (before its first plane)
+// and before any reads the new one (after the last plane).
+//
 // MASKED: the stripe's data end is not dword aligned (an object's last stripe only).
 template <bool MASKED>
 __global__ void __launch_bounds__(kWaves * 64, 4) enc_dma_kernel(EncArgs a) {
@@ -221,91 +260,35 @@ __global__ void __launch_bounds__(kWaves * 64, 4) enc_dma_kernel(EncArgs a) {
     const uint32_t lds0 = __builtin_amdgcn_groupstaticsize();  // LDS address of the dynamic array
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
+    uint32_t *const mail = lds + kMailBase / 4u;
 
-    const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
-    const uint32_t split = a.z0_split ? a.z0_split : 1u;
-    const uint32_t job = tile / split, part = tile - job * split;
-    const uint32_t z0b = a.z0_count ? a.z0_first + part * a.z0_count : 0u;
-    const uint32_t z0e = a.z0_count ? min(z0b + a.z0_count, a.z0_limit ? a.z0_limit : (uint32_t)kQ) : (uint32_t)kQ;
-    const uint32_t zb = z0b * kQ, ze = z0e * kQ;  // this workgroup's planes [zb, ze)
-    const EncJob J = a.jobs[job];
     const uint32_t cs = a.cs, sc = a.sc, slen = a.slice_len;
+    const uint32_t ntasks = a.ntasks;
     // lane word: columns 4w..4w+3 of every row; words past the 1,440-column image alias the
     // last one (same inputs, same values, same staging address)
     const uint32_t w = threadIdx.x < RB * 4u ? threadIdx.x : RB * 4u - 1u;
     const uint32_t colw = w * 4u;
+    // descriptors through scalar loads (constant address space): the compute waves must issue no
+    // vector load, or the compiler's waits for it would drain their stores
+    typedef const __attribute__((address_space(4))) EncJob cJob;
 
-    // Input resource: from J.src rounded down to 4 bytes to the stripe's last data byte, so the
-    // range check supplies Slicer::encode's zero padding (slicer.rs:276-283).
-    const uint32_t src_len = (uint32_t)J.src_len;
-    const uint32_t src_al = (uint32_t)reinterpret_cast<uintptr_t>(J.src) & 3u;
-    const uint32_t src_range = MASKED ? (src_len + src_al + 3u) & ~3u : src_len + src_al;
-    const u32x4 rs_src = rsrc(J.src - src_al, src_range);
-    const __amdgpu_buffer_rsrc_t rb_src =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(J.src - src_al), 0, (int)src_range, 0x00020000);
-    const uint32_t dst_range = a.n * slen - J.dst_skew;  // < 2^31, host-checked
-    const u32x4 rs_dst = rsrc(J.dst, dst_range);
-    const __amdgpu_buffer_rsrc_t rb_dst = __builtin_amdgcn_make_buffer_rsrc(J.dst, 0, (int)dst_range, 0x00020000);
-#if TEC_DMA_JX
-    // (measurement) the destination base's line offset, and a resource from the line it starts in
-    const uint32_t jx_base = (uint32_t)(reinterpret_cast<uintptr_t>(J.dst) & 127u);
-    const __amdgpu_buffer_rsrc_t rb_jx =
-        __builtin_amdgcn_make_buffer_rsrc(J.dst - jx_base, 0, (int)(dst_range + jx_base), 0x00020000);
-#endif
-    const uint32_t store_mask = J.store_mask;  // chunks to write (internal nodes)
-    uint32_t sl_lane = lane + J.rot;
-    sl_lane = (sl_lane >= 20u ? sl_lane - 20u : sl_lane) * slen;
-    auto slice_off = [&](uint32_t node) -> uint32_t { return __builtin_amdgcn_readlane(sl_lane, node); };
-
-    // The one word of the stripe that straddles the data end reads short through the range check
-    // (it is checked per dword of the load): fetched here with aligned pairs (+ byte mask) and
-    // substituted where its row is used.
-    const uint32_t last = src_len ? src_len - 1u : 0u;
-    const uint32_t ex = src_len ? last / cs : 0xffffu, ez = src_len ? (last - ex * cs) / sc : 0xffffu;
-    uint32_t fixw = 0;
-    if (src_len) {
-        const uint32_t off = ex * cs + ez * sc + colw, o = src_al + off;
-        const uint32_t lo = __builtin_amdgcn_raw_buffer_load_b32(rb_src, (int)(o & ~3u), 0, 0);
-        const uint32_t hi = __builtin_amdgcn_raw_buffer_load_b32(rb_src, (int)((o & ~3u) + 4u), 0, 0);
-        fixw = __builtin_amdgcn_alignbyte(hi, lo, o & 3u);
-        if constexpr (MASKED) {
-            const int rem = (int)src_len - (int)off;
-            fixw &= rem >= 4 ? 0xffffffffu : (rem <= 0 ? 0u : (1u << (8 * rem)) - 1u);
-        }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::"v"(fixw) : "memory");
-
-    // DMA pieces of the loader wave: instruction i of the 23 per plane (0..9 own rows, 10..22
-    // partner rows).  dvo = per-lane source offset (partner: for x = p; +10 sc when the piece's
-    // partner row index p >= z0 skips the red node).
-    uint32_t dvo[kDmaInstr];
-#pragma unroll
-    for (int i = 0; i < kDmaInstr; i++) {
-        dvo[i] = kDrop;
-        if (i < kOwnInstr) {
-            const uint32_t b = 64u * i + lane, x = b / RB, j = b - x * RB;
-            if (b < (uint32_t)K * RB) dvo[i] = x * cs + 16u * j;
-        } else {
-            const uint32_t b = 64u * (i - kOwnInstr) + lane, p = b / RB, j = b - p * RB;
-            if (b < 9u * RB) dvo[i] = p * kQ * sc + 16u * j;  // 16 j < 10 sc: p >= z0 <=> dvo >= 10 sc z0
-        }
-    }
-    // DMA of plane tp into ring slot `slot`: own rows from the input; partner rows C(z0, (x, s)),
-    // x != z0: the input chunk z0 at level 1, node z0's slice at level 2 (level-1 parity rows
-    // and parked U, written >= 8 steps earlier -- complete by the vmcnt waits below; nt loads
-    // skip this CU's L1).
-    // per-row pieces (TEC_DMA_ROWPOL): lane l's block l of the row (first instruction) and block
+    // per-row DMA pieces (TEC_DMA_ROWPOL): lane l's block l of the row (first instruction) and block
     // 64 + l (second, lanes < RB - 64)
     const uint32_t rvo0 = 16u * lane, rvo1 = lane < RB - 64u ? 16u * (64u + lane) : kDrop;
-    auto issue_rows = [&](uint32_t tp, uint32_t slot) {
+    // DMA of plane tp of task T into ring slot `slot`: own rows from the input; partner rows
+    // C(z0, (x, s)), x != z0: the input chunk z0 at level 1, node z0's slice at level 2 (level-1
+    // parity rows and parked U, written >= 8 steps earlier -- complete by the vmcnt waits below; nt
+    // loads skip this CU's L1).
+    auto issue_rows = [&](const LTask &T, uint32_t tp, uint32_t slot) {
         const uint32_t nz0 = tp / kQ, ns = tp - nz0 * kQ;
         const bool lvl2 = nz0 >= (uint32_t)K;
-        const uint32_t so_own = src_al + tp * sc;
-        const uint32_t so_pbase = lvl2 ? slice_off(nz0) + ns * sc : src_al + nz0 * cs + ns * sc;
+        const uint32_t so_own = T.src_al + tp * sc;
+        const uint32_t so_pbase =
+            lvl2 ? __builtin_amdgcn_readlane(T.sl_lane, nz0) + ns * sc : T.src_al + nz0 * cs + ns * sc;
         auto piece = [&](bool from_dst, bool nt, uint32_t so, uint32_t ld) {
             so = __builtin_amdgcn_readfirstlane(so);
             ld = __builtin_amdgcn_readfirstlane(lds0 + ld);
-            const u32x4 rs = from_dst ? rs_dst : rs_src;
+            const u32x4 rs = from_dst ? T.rs_dst : T.rs_src;
             if (nt) dma16<true>(rs, rvo0, so, ld);
             else dma16<false>(rs, rvo0, so, ld);
             if (rvo1 != kDrop) {
@@ -326,31 +309,131 @@ __global__ void __launch_bounds__(kWaves * 64, 4) enc_dma_kernel(EncArgs a) {
                   slot + kPartBase + p * RW);
         }
     };
-    auto issue_dma = [&](uint32_t tp, uint32_t slot) {
+    // the packed variant (TEC_DMA_ROWPOL 0): instruction i of the 23 per plane (0..9 own rows,
+    // 10..22 partner rows); the partner pieces skip the red node (+10 sc from partner row z0 on)
+    auto issue_dma = [&](const LTask &T, uint32_t tp, uint32_t slot) {
         if constexpr (TEC_DMA_ROWPOL != 0) {
-            issue_rows(tp, slot);
+            issue_rows(T, tp, slot);
             return;
         }
         const uint32_t nz0 = tp / kQ, ns = tp - nz0 * kQ;
-        const uint32_t so_own = __builtin_amdgcn_readfirstlane(src_al + tp * sc);
+        const uint32_t so_own = __builtin_amdgcn_readfirstlane(T.src_al + tp * sc);
         const bool lvl2 = nz0 >= (uint32_t)K;
-        const uint32_t so_part = __builtin_amdgcn_readfirstlane(lvl2 ? slice_off(nz0) + ns * sc : src_al + nz0 * cs + ns * sc);
+        const uint32_t so_part = __builtin_amdgcn_readfirstlane(
+            lvl2 ? __builtin_amdgcn_readlane(T.sl_lane, nz0) + ns * sc : T.src_al + nz0 * cs + ns * sc);
         const uint32_t skip = kQ * sc, skip_from = skip * nz0;
 #pragma unroll
         for (int i = 0; i < kDmaInstr; i++) {
             // lanes past the region's last block are masked off (an LDS-DMA lane that is merely
             // range-dropped still writes zeros to its LDS destination)
-            if (dvo[i] == kDrop) continue;
             if (i < kOwnInstr) {
-                dma16<false>(rs_src, dvo[i], so_own, __builtin_amdgcn_readfirstlane(lds0 + slot + 1024u * i));
+                const uint32_t b = 64u * i + lane, x = b / RB, j = b - x * RB;
+                if (b >= (uint32_t)K * RB) continue;
+                dma16<false>(T.rs_src, x * cs + 16u * j, so_own, __builtin_amdgcn_readfirstlane(lds0 + slot + 1024u * i));
             } else {
-                const uint32_t vo = dvo[i] + (dvo[i] >= skip_from ? skip : 0u);
+                const uint32_t b = 64u * (i - kOwnInstr) + lane, p = b / RB, j = b - p * RB;
+                if (b >= 9u * RB) continue;
+                const uint32_t d = p * kQ * sc + 16u * j;  // 16 j < 10 sc: p >= z0 <=> d >= 10 sc z0
+                const uint32_t vo = d + (d >= skip_from ? skip : 0u);
                 const uint32_t ld = __builtin_amdgcn_readfirstlane(lds0 + slot + kPartBase + 1024u * (i - kOwnInstr));
-                if (lvl2) dma16<true>(rs_dst, vo, so_part, ld);
-                else dma16<false>(rs_src, vo, so_part, ld);
+                if (lvl2) dma16<true>(T.rs_dst, vo, so_part, ld);
+                else dma16<false>(T.rs_src, vo, so_part, ld);
             }
         }
     };
+
+    if (wv == (uint32_t)G) {
+        // ---- the loader: the queue, every task's hand-over and every plane's DMA ----
+        // Task at queue position t (uniform): its DMA view, and its hand-over in mb[] -- the rows of
+        // planes, and the one word of the stripe that straddles the data end.  That word reads
+        // short through the range check (it is checked per dword of the load); it is fetched here
+        // with aligned pairs (+ byte mask) and substituted by the lane that owns it where its row
+        // is used.  Every word before it is whole in the image, every word after it is zero.
+        uint32_t mb[6];
+        auto fetch = [&](uint32_t t, LTask &T) {
+            const EncTask k = enc_task(t, ntasks, a.z0_first, a.z0_count, a.z0_split, a.z0_limit);
+            const uint32_t job = __builtin_amdgcn_readfirstlane(k.job);
+            cJob &J = *(cJob *)(uintptr_t)(a.jobs + job);
+            const uint8_t *src = J.src;
+            uint8_t *dst = J.dst;
+            // Input resource: from J.src rounded down to 4 bytes to the stripe's last data byte, so
+            // the range check supplies Slicer::encode's zero padding (slicer.rs:276-283).
+            const uint32_t src_len = (uint32_t)J.src_len;
+            const uint32_t src_al = (uint32_t)reinterpret_cast<uintptr_t>(src) & 3u;
+            const uint32_t src_range = MASKED ? (src_len + src_al + 3u) & ~3u : src_len + src_al;
+            T.rs_src = rsrc(src - src_al, src_range);
+            T.rs_dst = rsrc(dst, a.n * slen - J.dst_skew);  // < 2^31, host-checked
+            T.src_al = src_al;
+            uint32_t sl_lane = lane + J.rot;
+            T.sl_lane = (sl_lane >= 20u ? sl_lane - 20u : sl_lane) * slen;
+            T.zb = __builtin_amdgcn_readfirstlane(k.z0b * kQ);
+            T.ze = __builtin_amdgcn_readfirstlane(k.z0e * kQ);
+            mb[kMbJob] = job;
+            mb[kMbRows] = k.z0b | (k.z0e << 8);
+            mb[kMbWi] = mb[kMbEz] = mb[kMbEx] = 0xffffu;
+            mb[kMbFix] = 0;
+            if (src_len) {
+                const __amdgpu_buffer_rsrc_t rb_src =
+                    __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src - src_al), 0, (int)src_range, 0x00020000);
+                const uint32_t last = src_len - 1u;
+                const uint32_t ex = last / cs, ez = (last - ex * cs) / sc, wi = (last - ex * cs - ez * sc) / 4u;
+                const uint32_t off = ex * cs + ez * sc + wi * 4u, o = src_al + off;
+                const uint32_t lo = __builtin_amdgcn_raw_buffer_load_b32(rb_src, (int)(o & ~3u), 0, 0);
+                const uint32_t hi = __builtin_amdgcn_raw_buffer_load_b32(rb_src, (int)((o & ~3u) + 4u), 0, 0);
+                uint32_t fixw = __builtin_amdgcn_alignbyte(hi, lo, o & 3u);
+                if constexpr (MASKED) {
+                    const uint32_t rem = src_len - off;  // 1..4 bytes of the word are data
+                    fixw &= rem >= 4u ? 0xffffffffu : (1u << (8u * rem)) - 1u;
+                }
+                mb[kMbWi] = wi;
+                mb[kMbFix] = fixw;
+                mb[kMbEz] = ez;
+                mb[kMbEx] = ex;
+            }
+        };
+        auto post = [&](bool have) {  // the hand-over (every lane writes the same words)
+            mail[kMbJob] = have ? mb[kMbJob] : kNoTask;
+#pragma unroll
+            for (int i = 1; i < 6; i++) mail[i] = mb[i];
+        };
+        LTask cur, nxt;
+        fetch(blockIdx.x, cur);
+        post(true);  // (the compiler waits for the end word's loads here, before any DMA is issued)
+        // the first task's planes zb (even: plane z uses ring slot z & 1) and zb + 1, two planes ahead
+        issue_dma(cur, cur.zb, 0);
+        issue_dma(cur, cur.zb + 1u, kSlotBytes);
+        if (cur.zb != 0)  // a level-2 start (split launch) issues fewer rows per plane: wait for both
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        else if constexpr (TEC_DMA_ROWPOL != 0)
+            asm volatile("s_waitcnt vmcnt(32) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // plane 0 landed (16 rows x 2)
+        else
+            asm volatile("s_waitcnt vmcnt(23) lgkmcnt(0)\n\ts_barrier" ::: "memory");  // plane 0 landed
+        const bool queued = gridDim.x < ntasks;  // else one workgroup per task: nothing to draw
+        uint32_t tn = kNoTask;
+        for (;;) {
+            bool have = false;
+            // the same number of iterations as the compute waves' plane loop: two barriers each
+            for (uint32_t z = cur.zb; z < cur.ze; z++) {
+                lds_barrier();                                    // B2
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // plane z + 1 (or the next task's) landed
+                if (z == cur.zb + 2u) post(have);                 // before B1: the loads of fetch() have landed too
+                lds_barrier();                                    // B1
+                if (z + 2u < cur.ze) issue_dma(cur, z + 2u, (z & 1u) * kSlotBytes);
+                else if (have) issue_dma(nxt, nxt.zb + (z + 2u - cur.ze), (z & 1u) * kSlotBytes);
+                if (z == cur.zb) {  // draw the next queue position (one lane, an ordinary vector atomic)
+                    tn = 0;
+                    if (queued && lane == 0) tn = atomicAdd(a.queue, 1u);
+                } else if (z == cur.zb + 1u) {
+                    tn = queued ? gridDim.x + __builtin_amdgcn_readfirstlane(tn) : kNoTask;
+                    have = tn < ntasks;
+                    if (have) fetch(tn, nxt);
+                }
+            }
+            if (!have) return;
+            cur = nxt;
+        }
+    }
+    asm volatile("s_barrier" ::: "memory");  // P
 
     // flush: lane block offsets of a row (16 B per lane; the row's last partial block is one more
     // lane storing the row's LAST 16 bytes -- overlap rewritten with the same bytes)
@@ -365,150 +448,163 @@ __global__ void __launch_bounds__(kWaves * 64, 4) enc_dma_kernel(EncArgs a) {
 #pragma unroll
     for (int i = 0; i < kSlots; i++) sl[i] = 0;
 
-    if (wv == (uint32_t)G) {
-        // the loader: every plane's DMA, two planes ahead of the compute; the barriers mirror
-        // the compute waves' B2 / B1 (the ring slot of plane z is free after B1 of z)
-        issue_dma(zb, 0);  // zb is even: plane z uses ring slot z & 1
-        issue_dma(zb + 1u, kSlotBytes);
-        if (zb != 0)  // a level-2 start (split launch) issues fewer rows per plane: wait for both
-            asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        else if constexpr (TEC_DMA_ROWPOL != 0)
-            asm volatile("s_waitcnt vmcnt(32)\n\ts_barrier" ::: "memory");  // plane 0 landed (16 rows x 2)
-        else
-            asm volatile("s_waitcnt vmcnt(23)\n\ts_barrier" ::: "memory");  // plane 0 landed
-        // the same number of iterations as the compute waves' plane loop: two barriers each
-        for (uint32_t z = zb; z < ze; z++) {
-            lds_barrier();                                  // B2
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // plane z + 1 landed
-            lds_barrier();                                  // B1
-            if (z + 2u < ze) issue_dma(z + 2u, (z & 1u) * kSlotBytes);
-        }
-        return;
-    }
-    asm volatile("s_barrier" ::: "memory");
-
     uint8_t *const stg = lds8 + kStageBase + colw;
-    for (uint32_t z0 = z0b; z0 < z0e; z0++) {
-        const bool lvl2 = z0 >= (uint32_t)K;
-        const uint32_t type = lvl2 ? z0 - (K - 1) : 0u;
-        for (uint32_t s = 0; s < (uint32_t)kQ; s++) {
-            const uint32_t z = z0 * kQ + s;
-            const uint32_t slot = (z & 1u) * kSlotBytes;
-            const uint8_t *img = lds8 + slot + colw;
-            // an output row of this step: staging row `r` (the flush table's numbering)
-            auto out = [&](int r, uint32_t v) { st32(stg + r * RW, v); };
-            // ---- compute ----
-            uint32_t own[K], part[kQ];
+    // One task per iteration, taken from the mailbox.  kStoreLag carries over from task to task
+    // unchanged: it bounds this wave's own stores in flight, and the slice rows a task reads back at
+    // level 2 are rows of its own stripe that this workgroup stored during the same task.
+    for (;;) {
+        const uint32_t job = __builtin_amdgcn_readfirstlane(mail[kMbJob]);
+        if (job == kNoTask) break;
+        const uint32_t rows = __builtin_amdgcn_readfirstlane(mail[kMbRows]);
+        const uint32_t z0b = rows & 0xffu, z0e = rows >> 8;
+        const uint32_t ez = __builtin_amdgcn_readfirstlane(mail[kMbEz]);
+        const uint32_t ex = __builtin_amdgcn_readfirstlane(mail[kMbEx]);
+        const uint32_t fixw = __builtin_amdgcn_readfirstlane(mail[kMbFix]);
+        const bool fixl = w == __builtin_amdgcn_readfirstlane(mail[kMbWi]);  // this lane owns the end word
+        cJob &J = *(cJob *)(uintptr_t)(a.jobs + job);
+        uint8_t *const jdst = J.dst;
+        const uint32_t dst_range = a.n * slen - J.dst_skew;  // < 2^31, host-checked
+        const __amdgpu_buffer_rsrc_t rb_dst = __builtin_amdgcn_make_buffer_rsrc(jdst, 0, (int)dst_range, 0x00020000);
+#if TEC_DMA_JX
+        // (measurement) the destination base's line offset, and a resource from the line it starts in
+        const uint32_t jx_base = (uint32_t)(reinterpret_cast<uintptr_t>(jdst) & 127u);
+        const __amdgpu_buffer_rsrc_t rb_jx =
+            __builtin_amdgcn_make_buffer_rsrc(jdst - jx_base, 0, (int)(dst_range + jx_base), 0x00020000);
+#endif
+        const uint32_t store_mask = J.store_mask;  // chunks to write (internal nodes)
+        uint32_t sl_lane = lane + J.rot;
+        sl_lane = (sl_lane >= 20u ? sl_lane - 20u : sl_lane) * slen;
+        auto slice_off = [&](uint32_t node) -> uint32_t { return __builtin_amdgcn_readlane(sl_lane, node); };
+
+        for (uint32_t z0 = z0b; z0 < z0e; z0++) {
+            const bool lvl2 = z0 >= (uint32_t)K;
+            const uint32_t type = lvl2 ? z0 - (K - 1) : 0u;
+            for (uint32_t s = 0; s < (uint32_t)kQ; s++) {
+                const uint32_t z = z0 * kQ + s;
+                const uint32_t slot = (z & 1u) * kSlotBytes;
+                const uint8_t *img = lds8 + slot + colw;
+                // an output row of this step: staging row `r` (the flush table's numbering)
+                auto out = [&](int r, uint32_t v) { st32(stg + r * RW, v); };
+                // ---- compute ----
+                uint32_t own[K], part[kQ];
 #pragma unroll
-            for (int x = 0; x < K; x++) own[x] = lds32(img + x * RW);
-            if (z == ez) {  // end-row substitution, also patched into the image the flush copies
-                own[ex] = fixw;
-                st32(lds8 + slot + ex * RW + colw, fixw);
-            }
-            uint32_t acc[20 - K];
-            if (!lvl2) {
+                for (int x = 0; x < K; x++) own[x] = lds32(img + x * RW);
+                if (z == ez && fixl) {  // end-word substitution, also patched into the image the flush copies
 #pragma unroll
-                for (int x = 0; x < kQ; x++)
-                    part[x] = lds32(img + kPartBase + x * RW - ((uint32_t)x > z0 ? RW : 0u));
-                if (z0 == ex && s == ez % kQ) part[ez / kQ] = fixw;
-                uint32_t u[K];
+                    for (int x = 0; x < K; x++)
+                        if ((uint32_t)x == ex) own[x] = fixw;
+                    st32(lds8 + slot + ex * RW + colw, fixw);
+                }
+                uint32_t acc[20 - K];
+                if (!lvl2) {
 #pragma unroll
-                for (int x = 0; x < K; x++) u[x] = (uint32_t)x == z0 ? own[x] : pft3(own[x], part[x]);
-                enc::mds7_slp<true>(u, acc);
+                    for (int x = 0; x < kQ; x++)
+                        part[x] = lds32(img + kPartBase + x * RW - ((uint32_t)x > z0 ? RW : 0u));
+                    if (z0 == ex && s == ez % kQ && fixl) {
 #pragma unroll
-                for (int r = 0; r < 3; r++)
-                    out(kRowC0 + r, acc[r] ^ mulc(kPft.t_p[1], part[K + r]));
-            } else {
+                        for (int x = 0; x < kQ; x++)
+                            if ((uint32_t)x == ez / kQ) part[x] = fixw;
+                    }
+                    uint32_t u[K];
 #pragma unroll
-                for (int x = 0; x < 9; x++) part[x] = lds32(img + kPartBase + x * RW);
-                uint32_t u[K];
+                    for (int x = 0; x < K; x++) u[x] = (uint32_t)x == z0 ? own[x] : pft3(own[x], part[x]);
+                    enc::mds7_slp<true>(u, acc);
 #pragma unroll
-                for (int x = 0; x < K; x++) u[x] = pft3(own[x], part[x]);
-                enc::mds7_slp<false>(u, acc);
-                const uint32_t i0 = z0 - K;
+                    for (int r = 0; r < 3; r++)
+                        out(kRowC0 + r, acc[r] ^ mulc(kPft.t_p[1], part[K + r]));
+                } else {
 #pragma unroll
-                for (int r = 0; r < 3; r++) {
-                    // r < i0: pair with U(z0, (7+r, s)) parked in the slice; r == i0: red;
-                    // r > i0: park U(7+r, (z0, s)) (staged like an output row)
-                    if (r < 2) {
-                        const uint32_t us = part[K + r], up = acc[r];
-                        const uint32_t tt = xt(us ^ up);
-                        // C(z0, (7+r, s)): a row only for r < i0 (staged unconditionally, flushed
-                        // only then)
-                        out(kRowX + r, us ^ tt);
-                        out(kRowC0 + r, (uint32_t)r < i0 ? up ^ tt : up);  // C / U(7+r, (z0, s))
-                    } else {
-                        out(kRowC0 + r, acc[r]);
+                    for (int x = 0; x < 9; x++) part[x] = lds32(img + kPartBase + x * RW);
+                    uint32_t u[K];
+#pragma unroll
+                    for (int x = 0; x < K; x++) u[x] = pft3(own[x], part[x]);
+                    enc::mds7_slp<false>(u, acc);
+                    const uint32_t i0 = z0 - K;
+#pragma unroll
+                    for (int r = 0; r < 3; r++) {
+                        // r < i0: pair with U(z0, (7+r, s)) parked in the slice; r == i0: red;
+                        // r > i0: park U(7+r, (z0, s)) (staged like an output row)
+                        if (r < 2) {
+                            const uint32_t us = part[K + r], up = acc[r];
+                            const uint32_t tt = xt(us ^ up);
+                            // C(z0, (7+r, s)): a row only for r < i0 (staged unconditionally, flushed
+                            // only then)
+                            out(kRowX + r, us ^ tt);
+                            out(kRowC0 + r, (uint32_t)r < i0 ? up ^ tt : up);  // C / U(7+r, (z0, s))
+                        } else {
+                            out(kRowC0 + r, acc[r]);
+                        }
+                    }
+                }
+                switch (s) {
+                    case 0: col1<0>(acc + 3, sl, out); break;
+                    case 1: col1<1>(acc + 3, sl, out); break;
+                    case 2: col1<2>(acc + 3, sl, out); break;
+                    case 3: col1<3>(acc + 3, sl, out); break;
+                    case 4: col1<4>(acc + 3, sl, out); break;
+                    case 5: col1<5>(acc + 3, sl, out); break;
+                    case 6: col1<6>(acc + 3, sl, out); break;
+                    case 7: col1<7>(acc + 3, sl, out); break;
+                    case 8: col1<8>(acc + 3, sl, out); break;
+                    default: col1<9>(acc + 3, sl, out); break;
+                }
+                lds_barrier();  // B2: the plane's rows are staged
+                // ---- flush: this wave's share, read now, stored after B1 ----
+                const FlushTab::W &F = kFlush.w[type][s][wv];
+                const uint32_t n = F.n;
+                u32x4 d0[kCap], d1[kCap];
+                uint32_t dst[kCap];
+#pragma unroll
+                for (int q = 0; q < kCap; q++) {
+                    if ((uint32_t)q < n) {
+                        const uint32_t it = F.item[q];
+                        const uint32_t src = it & 0xffu;
+                        const uint8_t *row = (src & 0x80u) ? lds8 + slot + (src & 0x7fu) * RW : lds8 + kStageBase + src * RW;
+                        d0[q] = *reinterpret_cast<const u32x4 *>(row + lo0);
+                        d1[q] = *reinterpret_cast<const u32x4 *>(row + lo1);
+                        const uint32_t node = (it >> 8) & 0xffu, tz0 = (it >> 16) & 0xffu, ts = it >> 24;
+                        dst[q] = slice_off(node) + ((tz0 == 0xffu ? z0 : tz0) * kQ + (ts == 0xffu ? s : ts)) * sc;
+                        if (!((store_mask >> node) & 1u)) dst[q] = kDrop;  // a chunk the caller does not keep
+                    }
+                }
+                // B1: the next plane's DMA has landed and every wave is done reading this slot and the
+                // staging rows; the compute waves issue no loads, so they only bound their stores in
+                // flight (see kStoreLag)
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kStoreLag) : "memory");
+                lds_barrier();
+#pragma unroll
+                for (int q = 0; q < kCap; q++) {
+                    if ((uint32_t)q < n) {
+#if TEC_DMA_JX
+                        // measurement only (wrong bytes): the row's stores as whole 128-B lines, every
+                        // junction line once -- the write pattern of line-exact stores, to price them
+                        const uint32_t ab = jx_base + dst[q], first = (ab + 127u) & ~127u;
+                        const uint32_t o0 = first + 16u * lane - jx_base, o1 = first + 16u * (64u + lane) - jx_base;
+                        const uint32_t lim = ((ab + (uint32_t)sc + 127u) & ~127u) - jx_base;
+                        __builtin_amdgcn_raw_buffer_store_b128(d0[q], rb_jx, (int)(dst[q] == kDrop ? kDrop : o0), 0, kStAux);
+                        __builtin_amdgcn_raw_buffer_store_b128(d1[q], rb_jx, (int)(dst[q] == kDrop || o1 >= lim ? kDrop : o1), 0, kStAux);
+#else
+                        __builtin_amdgcn_raw_buffer_store_b128(d0[q], rb_dst, (int)vo0, (int)dst[q], kStAux);
+                        __builtin_amdgcn_raw_buffer_store_b128(d1[q], rb_dst, (int)vo1, (int)dst[q], kStAux);
+#endif
                     }
                 }
             }
-            switch (s) {
-                case 0: col1<0>(acc + 3, sl, out); break;
-                case 1: col1<1>(acc + 3, sl, out); break;
-                case 2: col1<2>(acc + 3, sl, out); break;
-                case 3: col1<3>(acc + 3, sl, out); break;
-                case 4: col1<4>(acc + 3, sl, out); break;
-                case 5: col1<5>(acc + 3, sl, out); break;
-                case 6: col1<6>(acc + 3, sl, out); break;
-                case 7: col1<7>(acc + 3, sl, out); break;
-                case 8: col1<8>(acc + 3, sl, out); break;
-                default: col1<9>(acc + 3, sl, out); break;
-            }
-            lds_barrier();  // B2: the plane's rows are staged
-            // ---- flush: this wave's share, read now, stored after B1 ----
-            const FlushTab::W &F = kFlush.w[type][s][wv];
-            const uint32_t n = F.n;
-            u32x4 d0[kCap], d1[kCap];
-            uint32_t dst[kCap];
-#pragma unroll
-            for (int q = 0; q < kCap; q++) {
-                if ((uint32_t)q < n) {
-                    const uint32_t it = F.item[q];
-                    const uint32_t src = it & 0xffu;
-                    const uint8_t *row = (src & 0x80u) ? lds8 + slot + (src & 0x7fu) * RW : lds8 + kStageBase + src * RW;
-                    d0[q] = *reinterpret_cast<const u32x4 *>(row + lo0);
-                    d1[q] = *reinterpret_cast<const u32x4 *>(row + lo1);
-                    const uint32_t node = (it >> 8) & 0xffu, tz0 = (it >> 16) & 0xffu, ts = it >> 24;
-                    dst[q] = slice_off(node) + ((tz0 == 0xffu ? z0 : tz0) * kQ + (ts == 0xffu ? s : ts)) * sc;
-                    if (!((store_mask >> node) & 1u)) dst[q] = kDrop;  // a chunk the caller does not keep
-                }
-            }
-            // B1: the next plane's DMA has landed and every wave is done reading this slot and the
-            // staging rows; the compute waves issue no loads, so they only bound their stores in
-            // flight (see kStoreLag)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kStoreLag) : "memory");
-            lds_barrier();
-#pragma unroll
-            for (int q = 0; q < kCap; q++) {
-                if ((uint32_t)q < n) {
-#if TEC_DMA_JX
-                    // measurement only (wrong bytes): the row's stores as whole 128-B lines, every
-                    // junction line once -- the write pattern of line-exact stores, to price them
-                    const uint32_t ab = jx_base + dst[q], first = (ab + 127u) & ~127u;
-                    const uint32_t o0 = first + 16u * lane - jx_base, o1 = first + 16u * (64u + lane) - jx_base;
-                    const uint32_t lim = ((ab + (uint32_t)sc + 127u) & ~127u) - jx_base;
-                    __builtin_amdgcn_raw_buffer_store_b128(d0[q], rb_jx, (int)(dst[q] == kDrop ? kDrop : o0), 0, kStAux);
-                    __builtin_amdgcn_raw_buffer_store_b128(d1[q], rb_jx, (int)(dst[q] == kDrop || o1 >= lim ? kDrop : o1), 0, kStAux);
-#else
-                    __builtin_amdgcn_raw_buffer_store_b128(d0[q], rb_dst, (int)vo0, (int)dst[q], kStAux);
-                    __builtin_amdgcn_raw_buffer_store_b128(d1[q], rb_dst, (int)vo1, (int)dst[q], kStAux);
-#endif
-                }
-            }
         }
-    }
-    // the last plane's left-over row (its staging row is untouched since the last compute)
-    if (wv == 0 && z0e == (uint32_t)kQ) {
-        const uint32_t it = kFlush.extra, src = it & 0xffu;
-        const uint8_t *row = lds8 + kStageBase + src * RW;
-        const u32x4 e0 = *reinterpret_cast<const u32x4 *>(row + lo0);
-        const u32x4 e1 = *reinterpret_cast<const u32x4 *>(row + lo1);
-        const uint32_t node = (it >> 8) & 0xffu, tz0 = (it >> 16) & 0xffu, ts = it >> 24;
-        const uint32_t d = ((store_mask >> node) & 1u)
-                               ? slice_off(node) + ((tz0 == 0xffu ? kQ - 1u : tz0) * kQ + (ts == 0xffu ? kQ - 1u : ts)) * sc
-                               : kDrop;
-        __builtin_amdgcn_raw_buffer_store_b128(e0, rb_dst, (int)vo0, (int)d, kStAux);
-        __builtin_amdgcn_raw_buffer_store_b128(e1, rb_dst, (int)vo1, (int)d, kStAux);
+        // the last plane's left-over row (its staging row is untouched since the last compute, and
+        // is next written at the ninth plane of the next task)
+        if (wv == 0 && z0e == (uint32_t)kQ) {
+            const uint32_t it = kFlush.extra, src = it & 0xffu;
+            const uint8_t *row = lds8 + kStageBase + src * RW;
+            const u32x4 e0 = *reinterpret_cast<const u32x4 *>(row + lo0);
+            const u32x4 e1 = *reinterpret_cast<const u32x4 *>(row + lo1);
+            const uint32_t node = (it >> 8) & 0xffu, tz0 = (it >> 16) & 0xffu, ts = it >> 24;
+            const uint32_t d = ((store_mask >> node) & 1u)
+                                   ? slice_off(node) + ((tz0 == 0xffu ? kQ - 1u : tz0) * kQ + (ts == 0xffu ? kQ - 1u : ts)) * sc
+                                   : kDrop;
+            __builtin_amdgcn_raw_buffer_store_b128(e0, rb_dst, (int)vo0, (int)d, kStAux);
+            __builtin_amdgcn_raw_buffer_store_b128(e1, rb_dst, (int)vo1, (int)d, kStAux);
+        }
     }
 }
 
@@ -516,9 +612,34 @@ __global__ void __launch_bounds__(kWaves * 64, 4) enc_dma_kernel(EncArgs a) {
 
 bool encode_dma_supported(int n, int k, uint32_t sc) { return n == 20 && k == 7 && sc > 1280u && sc <= 1440u && sc % 2 == 0; }
 
-hipError_t launch_encode_dma(bool masked, const EncArgs &a, hipStream_t s) {
-    if (a.njobs == 0) return hipSuccess;
-    if (!encode_dma_supported((int)a.n, 7, a.sc) || a.njobs > 0x7fffffffu) return hipErrorInvalidValue;
+// Resident workgroups of an encode launch on the current device: two per CU (the kernel's LDS),
+// queried once per device.  Measurement knob TEC_DEBUG_KNOBS=1 TEC_ENC_GRID=g: g workgroups ("cu":
+// the default; 0: one per task, the queue unused -- the launch shape before the stripe queue,
+// which this kernel runs 1.6 % slower than the kernel before it did).
+static uint32_t enc_slots() {
+    const char *e = tec_knob("TEC_ENC_GRID");
+    if (e && strcmp(e, "cu") != 0) {
+        const long v = atol(e);
+        return v < 0 ? 0u : (uint32_t)v;
+    }
+    static std::atomic<uint32_t> cached[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    uint32_t v = cached[dev].load(std::memory_order_relaxed);
+    if (!v) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        v = 2u * (uint32_t)cus;
+        cached[dev].store(v, std::memory_order_relaxed);
+    }
+    return v;
+}
+
+uint32_t encode_dma_grid(const EncArgs &a) { return enc_grid(enc_task_count(a), enc_slots()); }
+
+hipError_t launch_encode_dma(bool masked, const EncArgs &a0, hipStream_t s) {
+    if (a0.njobs == 0) return hipSuccess;
+    if (!encode_dma_supported((int)a0.n, 7, a0.sc) || a0.njobs > 0x7fffffffu) return hipErrorInvalidValue;
     const void *fn = masked ? reinterpret_cast<const void *>(dma::enc_dma_kernel<true>)
                             : reinterpret_cast<const void *>(dma::enc_dma_kernel<false>);
 #ifndef TEC_DMA_LDS_PAD
@@ -529,16 +650,20 @@ hipError_t launch_encode_dma(bool masked, const EncArgs &a, hipStream_t s) {
     if (e != hipSuccess) return e;
     // a plane range must start on an even plane (ring slot parity) and stay within the 100 planes
     // every part non-empty and within the 10 rows (a shorter last part when z0_limit cuts it)
-    if (a.z0_count) {
-        const uint32_t lim = a.z0_limit ? a.z0_limit : 10u;
-        if (a.z0_split == 0 || lim > 10u || a.z0_first + (a.z0_split - 1u) * a.z0_count >= lim) return hipErrorInvalidValue;
+    if (a0.z0_count) {
+        const uint32_t lim = a0.z0_limit ? a0.z0_limit : 10u;
+        if (a0.z0_split == 0 || lim > 10u || a0.z0_first + (a0.z0_split - 1u) * a0.z0_count >= lim) return hipErrorInvalidValue;
     }
-    const uint64_t grid = (uint64_t)a.njobs * (a.z0_count ? a.z0_split : 1u);
-    if (grid > 0x7fffffffu) return hipErrorInvalidValue;
+    const uint64_t ntasks = enc_task_count(a0);
+    if (ntasks > 0x7fffffffu) return hipErrorInvalidValue;
+    EncArgs a = a0;
+    a.ntasks = (uint32_t)ntasks;
+    // without a counter every task gets its own workgroup (the kernel then draws nothing)
+    const uint32_t grid = a.queue ? encode_dma_grid(a) : a.ntasks;
     if (masked)
-        hipLaunchKernelGGL(dma::enc_dma_kernel<true>, dim3((uint32_t)grid), dim3(dma::kWaves * 64), lds, s, a);
+        hipLaunchKernelGGL(dma::enc_dma_kernel<true>, dim3(grid), dim3(dma::kWaves * 64), lds, s, a);
     else
-        hipLaunchKernelGGL(dma::enc_dma_kernel<false>, dim3((uint32_t)grid), dim3(dma::kWaves * 64), lds, s, a);
+        hipLaunchKernelGGL(dma::enc_dma_kernel<false>, dim3(grid), dim3(dma::kWaves * 64), lds, s, a);
     return hipGetLastError();
 }
 

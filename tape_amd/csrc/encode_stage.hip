@@ -28,6 +28,7 @@
 //     address: program order), 30 rows per stripe.
 // Coefficients (generator, PFT) are constexpr: each GF product is a fixed XOR selection of
 // xtime multiples, or a 2-bit v_perm lookup with SGPR tables for one-off heavy constants.
+#include <algorithm>
 #include "kernels.hpp"
 #include "gf_dev.hpp"
 #include "dev_io.hpp"
@@ -567,8 +568,10 @@ __global__ void __launch_bounds__(G * 64, TEC_STAGE_WAVES_PER_EU) enc_stage_kern
 }  // namespace stage
 
 // Metadata suffix (metadata.rs:22-64): the 48-byte record into each of an object's n slices.
-__global__ void meta_kernel(const MetaJob *__restrict__ jobs, uint32_t njobs, uint32_t n) {
+__global__ void meta_kernel(const MetaJob *__restrict__ jobs, uint32_t njobs, uint32_t n, uint32_t *__restrict__ zero,
+                            uint32_t nzero) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nzero) zero[i] = 0;  // the call's stripe-queue counters (encode_dma.hip), read by later launches
     const uint32_t per = n * 6u;
     if (i >= njobs * per) return;
     const uint32_t j = i / per, r = i - j * per, sl = r / 6u, wd = r - sl * 6u;
@@ -581,10 +584,10 @@ __global__ void meta_kernel(const MetaJob *__restrict__ jobs, uint32_t njobs, ui
     }
 }
 
-hipError_t launch_meta(const MetaJob *jobs, uint32_t njobs, uint32_t n, hipStream_t s) {
-    if (!njobs) return hipSuccess;
-    const uint32_t total = njobs * n * 6u;
-    hipLaunchKernelGGL(meta_kernel, dim3((total + 255) / 256), dim3(256), 0, s, jobs, njobs, n);
+hipError_t launch_meta(const MetaJob *jobs, uint32_t njobs, uint32_t n, hipStream_t s, uint32_t *zero, uint32_t nzero) {
+    if (!njobs) return nzero ? hipMemsetAsync(zero, 0, (size_t)nzero * 4u, s) : hipSuccess;
+    const uint32_t total = std::max(njobs * n * 6u, nzero);
+    hipLaunchKernelGGL(meta_kernel, dim3((total + 255) / 256), dim3(256), 0, s, jobs, njobs, n, zero, nzero);
     return hipGetLastError();
 }
 

@@ -986,13 +986,27 @@ int encode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, 
         a.groups_per_wg = small ? 1u : 0u;
         scratch_bytes = std::max(scratch_bytes, encode_rows_scratch_bytes(a));
     }
+    // the LDS-DMA launches' stripe-queue counters (encode_dma.hip): one dword per launch, after the
+    // staged kernel's parking rows in the call's workspace
+    const bool split_call = (per_call && total_stripes <= g_enc_split) || g_enc_split_batch;
+    uint32_t nqueues = 0;
+    for (const Launch &L : launches)
+        if (dma_path(L)) nqueues += split_call ? 2u : 1u;
+    const size_t queue_off = (scratch_bytes + 255) & ~(size_t)255;
     uint8_t *scratch = nullptr;
-    if (scratch_bytes) {
-        r = A.workspace(scratch_bytes, s, &scratch);
+    if (scratch_bytes || nqueues) {
+        r = A.workspace(queue_off + (size_t)nqueues * 4u, s, &scratch);
         if (r) return r;
     }
+    uint32_t *const queues = reinterpret_cast<uint32_t *>(scratch + queue_off);
+    uint32_t qi = 0;
     KTimer kt(s);
-    if (!metas.empty()) TE_HIP(launch_meta(A.at<MetaJob>(meta_off), (uint32_t)metas.size(), (uint32_t)n, s));
+    // the counters are zero before every launch of the call: the metadata kernel runs first on the
+    // stream and clears them; a call without one (raw chunks, a keep filter) clears them with a memset
+    if (!metas.empty())
+        TE_HIP(launch_meta(A.at<MetaJob>(meta_off), (uint32_t)metas.size(), (uint32_t)n, s, queues, nqueues));
+    else if (nqueues)
+        TE_HIP(hipMemsetAsync(queues, 0, (size_t)nqueues * 4u, s));
     auto gpe_args = [&](size_t gi, const Launch &L, uint32_t word_base, uint32_t word_end) {
         const uint32_t cs = (uint32_t)L.key.cs, sc = cs / (uint32_t)h.alpha;
         (void)sc;
@@ -1029,13 +1043,15 @@ int encode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, 
             a.sc = sc;
             a.slice_len = (uint32_t)L.key.slice_len;
             a.n = (uint32_t)n;
-            if ((per_call && total_stripes <= g_enc_split) || g_enc_split_batch) {
+            a.queue = queues + qi++;
+            if (split_call) {
                 // level-1 rows z0 = 0..6: one workgroup each (or g_enc_split_batch rows each)
                 const uint32_t per = per_call ? 1u : g_enc_split_batch;
                 a.z0_first = 0; a.z0_count = per; a.z0_split = (7 + per - 1) / per; a.z0_limit = 7;
                 TE_HIP(launch_encode_dma(L.key.masked, a, s));
                 a.z0_limit = 0;
                 a.z0_first = 7; a.z0_count = 3; a.z0_split = 1;   // level 2 reads their parity back:
+                a.queue = queues + qi++;
                 level2.push_back({L.key.masked, a});              // after every level-1 launch
             } else {
                 TE_HIP(launch_encode_dma(L.key.masked, a, s));

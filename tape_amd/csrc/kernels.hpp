@@ -51,7 +51,48 @@ struct EncArgs {
     // level-2 rows (7..9, a chain) in a second launch.
     uint32_t z0_first, z0_count, z0_split;
     uint32_t z0_limit;     // a part's rows end at min(its start + z0_count, z0_limit) (0: no bound)
+    // encode_dma.hip's stripe queue: a launch has enc_task_count() tasks (a stripe's rows of planes,
+    // all ten or one part of them) and min(tasks, slots) workgroups; a workgroup's first task is
+    // its block index, every further one gridDim.x + atomicAdd(queue, 1).  `queue` is zero when
+    // the launch starts (the call's meta_kernel or a memset on the stream zeroes it); the
+    // launcher sets ntasks.
+    uint32_t *queue;
+    uint32_t ntasks;
 };
+
+// The LDS-DMA encode's tasks, shared by the kernel, the launcher and the host test
+// (tests/native/enc_queue_plan.cpp).  Queue position t of a launch of ntasks tasks is tile
+// enc_xcd_tile(t, ntasks) -- the workgroups of one XCD draw positions that are mostly congruent
+// mod 8, so each XCD still walks a contiguous run of stripes (speed only) -- and tile / split is
+// the stripe, tile % split its part: the rows of planes [z0b, z0e).
+struct EncTask {
+    uint32_t job, z0b, z0e;
+};
+__host__ __device__ inline uint32_t enc_xcd_tile(uint32_t b, uint32_t nb) {  // = dev_io.hpp xcd_tile
+    const uint32_t full = nb & ~7u;
+    if (b >= full) return b;
+    return (b & 7u) * (full >> 3) + (b >> 3);
+}
+__host__ __device__ inline uint32_t enc_task_split(uint32_t z0_count, uint32_t z0_split) {
+    return z0_count && z0_split ? z0_split : 1u;
+}
+__host__ __device__ inline EncTask enc_task(uint32_t t, uint32_t ntasks, uint32_t z0_first, uint32_t z0_count,
+                                            uint32_t z0_split, uint32_t z0_limit) {
+    const uint32_t tile = enc_xcd_tile(t, ntasks), split = enc_task_split(z0_count, z0_split);
+    EncTask k;
+    k.job = tile / split;
+    const uint32_t part = tile - k.job * split;
+    k.z0b = z0_count ? z0_first + part * z0_count : 0u;
+    const uint32_t lim = z0_limit ? z0_limit : 10u, e = k.z0b + z0_count;
+    k.z0e = z0_count ? (e < lim ? e : lim) : 10u;
+    return k;
+}
+inline uint64_t enc_task_count(const EncArgs &a) { return (uint64_t)a.njobs * enc_task_split(a.z0_count, a.z0_split); }
+// workgroups of a launch: `slots` resident ones (two per CU) draw from the queue; slots == 0 is one
+// workgroup per task (the queue then hands out nothing)
+inline uint32_t enc_grid(uint64_t ntasks, uint32_t slots) {
+    return (uint32_t)(slots && slots < ntasks ? slots : ntasks);
+}
 
 // Metadata suffix writer: one 48-byte record per object, copied to its n slices.
 struct MetaJob {
@@ -276,7 +317,11 @@ hipError_t launch_encode_rows(int k, bool masked, const EncArgs &a, hipStream_t 
 // encode_dma.hip: Clay(20,7,16), 1,280 < sub-chunk <= 1,440 bytes (the 1 MB stripes), no scratch
 bool encode_dma_supported(int n, int k, uint32_t sc);
 hipError_t launch_encode_dma(bool masked, const EncArgs &a, hipStream_t s);
-hipError_t launch_meta(const MetaJob *jobs, uint32_t njobs, uint32_t n, hipStream_t s);
+// workgroups launch_encode_dma starts for `a` on the current device when a.queue is set (< its tasks: the queue is drawn from)
+uint32_t encode_dma_grid(const EncArgs &a);
+// also zeroes zero[0 .. nzero) (the encode launches' stripe-queue counters of the same call)
+hipError_t launch_meta(const MetaJob *jobs, uint32_t njobs, uint32_t n, hipStream_t s, uint32_t *zero = nullptr,
+                       uint32_t nzero = 0);
 struct CopyJob {
     const uint8_t *src;
     uint8_t *dst;
