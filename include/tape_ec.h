@@ -125,6 +125,26 @@ int te_clay_set_decode_store_cap(te_clay *c, uint32_t max_patterns);
  * (those upload their patterns with the call instead). */
 int te_clay_decode_store_stats(te_clay *c, uint32_t *capacity, uint32_t *used, uint64_t *clears, uint64_t *grows,
                                uint64_t *arena_calls);
+/* Which kernels the handle's last decode call launched (diagnostics; host bookkeeping only, no
+ * effect on results): one te_clay_decode / te_slicer_decode / te_decode_batch_device /
+ * te_recover_batch_device call, summed over its parts and windows when a recover batch is split.
+ * Zeroed when such a call has passed its argument checks and starts its device work; all zero
+ * before the first one.  class_g is that of the call's last class launches, class_streams the
+ * most streams any part used. */
+#define TE_DECODE_CLASSES 24
+typedef struct te_decode_launch_stats {
+    uint32_t class_launches[TE_DECODE_CLASSES]; /* launches per class kernel: 0..7 decode (known
+                                                   column-0 nodes), 8 + 2*a0 + column: node recover */
+    uint64_t class_stripes;      /* stripes of those launches */
+    uint32_t class_g;            /* their column groups per workgroup: 1 per-call kernels, 2 batch
+                                    kernels (0: no class launch) */
+    uint32_t class_streams;      /* streams the class launches ran on side by side */
+    uint32_t table_launches, generic_launches, jit_launches;  /* table-driven, generic, pattern kernels */
+    uint32_t direct_out;         /* per-call decode: the kernels stored straight into the caller's
+                                    page-locked `out` (no staging copy) */
+    uint64_t table_stripes, generic_stripes, jit_stripes;
+} te_decode_launch_stats;
+int te_clay_decode_launch_stats(te_clay *c, te_decode_launch_stats *out);
 int te_clay_get_info(const te_clay *c, te_clay_info *out);
 /* ClayCoder::chunk_size_for  clay.rs:61-73 */
 size_t te_clay_chunk_size_for(const te_clay *c, size_t input_len);

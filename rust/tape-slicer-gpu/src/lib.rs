@@ -235,6 +235,14 @@ impl ClayCoder {
         if s != 0 { fatal(s) }
         (cap, used, cl, gr, ar)
     }
+    /// The kernels the last decode pass on this coder launched (class launches by class id, their
+    /// stripes, column groups and streams; table-driven, generic and pattern kernel launches).
+    pub fn decode_launch_stats(&self) -> ffi::te_decode_launch_stats {
+        let mut st = std::mem::MaybeUninit::<ffi::te_decode_launch_stats>::zeroed();
+        let s = unsafe { ffi::te_clay_decode_launch_stats(self.raw.as_ptr(), st.as_mut_ptr()) };
+        if s != 0 { fatal(s) }
+        unsafe { st.assume_init() }
+    }
 }
 
 impl ErasureCoder for ClayCoder {

@@ -78,6 +78,16 @@ class te_repair_object(C.Structure):
                 ("metadata", C.c_uint8 * 48)]
 
 
+DECODE_CLASSES = 24  # TE_DECODE_CLASSES
+
+
+class te_decode_launch_stats(C.Structure):
+    _fields_ = [("class_launches", C.c_uint32 * DECODE_CLASSES), ("class_stripes", C.c_uint64),
+                ("class_g", C.c_uint32), ("class_streams", C.c_uint32), ("table_launches", C.c_uint32),
+                ("generic_launches", C.c_uint32), ("jit_launches", C.c_uint32), ("direct_out", C.c_uint32),
+                ("table_stripes", C.c_uint64), ("generic_stripes", C.c_uint64), ("jit_stripes", C.c_uint64)]
+
+
 def build(verbose: bool = False) -> str:
     """Compile libtapeec.so for gfx950 with hipcc (make -C tape_amd)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True,
@@ -110,6 +120,7 @@ def _load() -> C.CDLL:
         "te_clay_decode_jit_status": (i, [vp, u32, u32p, u32p, u32p]),
         "te_clay_set_decode_store_cap": (i, [vp, u32]),
         "te_clay_decode_store_stats": (i, [vp, u32p, u32p, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
+        "te_clay_decode_launch_stats": (i, [vp, C.POINTER(te_decode_launch_stats)]),
         "te_version": (C.c_char_p, []),
         "te_kernel_timing": (C.c_int, [C.c_int]),
         "te_kernel_time_ms": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),

@@ -152,8 +152,9 @@ struct DecClassGenOpt {
                               // 420 uniform branches per kernel cost more scheduling than the rows)
 };
 
+// nring_out: the per-call kernel's ring rows per step, as the kernel registers them.
 inline std::string dec_class_source(const ClayHost &h, int id, uint8_t t_u, DecProgHdr &Hout,
-                                    const DecClassGenOpt &opt = DecClassGenOpt()) {
+                                    const DecClassGenOpt &opt = DecClassGenOpt(), uint32_t *nring_out = nullptr) {
     GpePattern P;
     DecProgHdr H;
     std::vector<DecStep> steps;
@@ -199,6 +200,7 @@ inline std::string dec_class_source(const ClayHost &h, int id, uint8_t t_u, DecP
         for (int e = 0; e < NE; e++) c += S.ek[e] == kErType1 || S.ek[e] == kErType1U;
         nring = std::max(nring, c);
     }
+    if (nring_out) *nring_out = nring;
     auto body = [&](bool small) {
     const int depth = small ? opt.deep : 1, W = small ? kDecClassSplit : 1;
     // the per-call kernel: W compute waves share one 64-column group and a loader wave (wv == W)

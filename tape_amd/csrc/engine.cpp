@@ -297,6 +297,10 @@ struct DevBuf {
 };
 
 struct HostBuf {  // pinned staging (descriptor uploads, the per-call entry points' host side)
+    // hipHostMalloc memory: under unified addressing the host pointer it returns is also the
+    // pointer kernels use (hipHostGetDevicePointer gives it back unchanged), which the zero-copy
+    // per-call paths rely on when they hand u8() to a kernel.  Memory a caller page-locked itself
+    // (hipHostRegister) has no such promise: host_device_ptr asks for its device address.
     void *p = nullptr;
     size_t cap = 0;
     uint8_t *u8() const { return static_cast<uint8_t *>(p); }
@@ -525,6 +529,9 @@ struct te_clay {
     static constexpr int kClsSide = 7;
     hipStream_t cls_s[kClsSide] = {};
     hipEvent_t cls_fork = nullptr, cls_join[kClsSide] = {};
+    // the decode_enqueue launches of the last decode / recover call (te_clay_decode_launch_stats):
+    // zeroed when the call starts its device work, summed over its decode_enqueue passes
+    te_decode_launch_stats dls{};
 };
 
 // Drain and free everything a handle holds on its device (on that device).
@@ -738,6 +745,13 @@ int te_clay_decode_store_stats(te_clay *c, uint32_t *capacity, uint32_t *used, u
     if (clears) *clears = c->dstore.clears;
     if (grows) *grows = c->dstore.grows;
     if (arena_calls) *arena_calls = c->dstore.arena_calls;
+    return TE_OK;
+}
+
+int te_clay_decode_launch_stats(te_clay *c, te_decode_launch_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->dls;
     return TE_OK;
 }
 
@@ -1283,6 +1297,8 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
     const ClayHost &h = c->h;
     const int n = h.n;
     const int rotated = (cfg && !raw) ? cfg->rotated : 0;
+    static_assert(TE_DECODE_CLASSES == kDecClasses, "te_decode_launch_stats counts every class");
+    te_decode_launch_stats &dls = c->dls;  // summed: the calling entry point zeroed it
     // compiled programs kept on the host: <= ~430 MB (26 KB per pattern, as many as the device
     // store's cap; 77,520 masks exist for k = 7, x 20 outputs for node recover)
     if (c->dec_cache.size() > std::max<size_t>(c->dstore.max_cap, nitems)) c->dec_cache.clear();
@@ -1662,6 +1678,8 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
     for (const Fixed &f : fixed) {
         const dfix_args a = fixed_args(f, scratch);
         TE_HIP(launch_dec_fixed(*f.k, a, dec_jit_geom(a.sc).G, s));
+        dls.jit_launches++;
+        dls.jit_stripes += f.jobs.size();
     }
     if (!cls.empty()) {
         // the class groups side by side on up to 1 + kClsSide streams, largest first, each with
@@ -1691,7 +1709,11 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
             TE_HIP(launch_dec_class(cg.id, A.at<GpeJob>(cg.off), pp, (uint32_t)cg.jobs.size(), sc, group_in_stride[cg.key],
                                     cs, (uint32_t)n, cls_scratch + scr_at, class_g, ss[k % (size_t)ns]));
             scr_at += dec_class_scratch_bytes(cg.id, (uint32_t)cg.jobs.size(), sc, class_g);
+            dls.class_launches[cg.id]++;
+            dls.class_stripes += cg.jobs.size();
         }
+        dls.class_g = class_g;
+        dls.class_streams = std::max(dls.class_streams, (uint32_t)ns);
         for (int i = 1; i < ns; i++) {
             TE_HIP(hipEventRecord(c->cls_join[i - 1], ss[i]));
             TE_HIP(hipStreamWaitEvent(s, c->cls_join[i - 1], 0));
@@ -1702,6 +1724,8 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
             DecArgs a = dec_args(o);
             a.scratch = scratch;
             TE_HIP(launch_decode_stage(a, s));
+            dls.table_launches++;
+            dls.table_stripes += a.njobs;
             continue;
         }
         const uint64_t cs = o.first >> 32;
@@ -1723,6 +1747,8 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
         a.out_mask = (h.k >= 64) ? ~0ull : ((1ull << h.k) - 1ull);
         for (int i = 0; i < 16; i++) a.qpow[i] = h.qpow[i];
         TE_HIP(launch_gpe(a, max_er, s));
+        dls.generic_launches++;
+        dls.generic_stripes += a.njobs;
     }
     kt.stop();
     if (in_store) TE_HIP(c->dstore.readers.record(s));  // a later call that empties the store waits for these launches
@@ -2248,6 +2274,17 @@ static bool host_pinned(const void *p) {
         return false;
     }
     return a.type == hipMemoryTypeHost;
+}
+// The address a kernel may use for page-locked host memory `p` (hipPointerAttribute_t's
+// devicePointer: HIP promises no other, and a registered range need not map at its host address),
+// or null when `p` is pageable or has no device mapping.
+static uint8_t *host_device_ptr(const void *p) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return a.type == hipMemoryTypeHost ? static_cast<uint8_t *>(a.devicePointer) : nullptr;
 }
 
 // Copy object o's n slices (slice_len bytes each, at dev / host) out in row pieces on stream s.
@@ -3169,6 +3206,7 @@ int te_decode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
         items[i].out_off = objs[i].out_off;
     }
     std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     return decode_enqueue(c, cfg, d_slices, items.data(), items.size(), d_out, (hipStream_t)stream, false);
@@ -3196,12 +3234,17 @@ int te_repair_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair
 // Slicer::encode's stripe, slicer.rs:276-283), so only stripes whose lost shard is a parity
 // shard are re-encoded.  Objects go through the device workspaces in windows (bounded memory);
 // the workspaces are ordered against a previous call on another stream by `rec_done`.
-int te_recover_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
-                            const te_recover_object *objs, const uint8_t *h_meta, size_t nobj, uint8_t *d_out,
-                            void *stream) {
+}  // extern "C"
+// part = a subset of a mixed batch, called from the whole batch's call: the launch stats go on summing
+static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_object *objs,
+                         const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool part) {
     if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
     if (nobj == 0) return TE_OK;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    if (!part) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        c->dls = te_decode_launch_stats{};
+    }
     const ClayHost &h = c->h;
     const uint32_t n = (uint32_t)h.n;
     const int rotated = cfg->rotated;
@@ -3245,7 +3288,7 @@ int te_recover_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t 
                     o.push_back(objs[i]);
                     m.insert(m.end(), h_meta + i * TE_META_SIZE, h_meta + (i + 1) * TE_META_SIZE);
                 }
-                const int r = te_recover_batch_device(c, cfg, d_slices, o.data(), m.data(), o.size(), d_out, stream);
+                const int r = recover_batch(c, cfg, d_slices, o.data(), m.data(), o.size(), d_out, stream, true);
                 if (r) return r;
             }
             return TE_OK;
@@ -3415,6 +3458,13 @@ int te_recover_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t 
     c->rec_stream = s;
     return r ? r : r2;
 }
+extern "C" {
+
+int te_recover_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                            const te_recover_object *objs, const uint8_t *h_meta, size_t nobj, uint8_t *d_out,
+                            void *stream) {
+    return recover_batch(c, cfg, d_slices, objs, h_meta, nobj, d_out, stream, false);
+}
 
 int te_slicer_encode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *data, size_t len, uint8_t *slices,
                      size_t cap) {
@@ -3514,6 +3564,7 @@ int te_clay_decode(te_clay *c, const uint8_t *const *chunks, size_t cs, uint8_t 
     if (cs == 0 || cs % (size_t)h.alpha) return TE_ERR_BAD_ENCODING;
     if (cap < (size_t)h.k * cs) return TE_ERR_BUFFER_TOO_SMALL;
     std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     int r = ensure_stream(c);
@@ -3530,13 +3581,15 @@ int te_clay_decode(te_clay *c, const uint8_t *const *chunks, size_t cs, uint8_t 
         for (int i = 0; i < h.n; i++)
             if (chunks[i]) segs.push_back({c->hio_in.u8() + (size_t)i * cs, chunks[i], cs});
         copy_pool(c->device).run(segs);
-        const bool out_pinned = host_pinned(out);
-        if (!out_pinned) TE_HIP(c->hio_out.ensure((size_t)h.k * cs));
-        uint8_t *dst = out_pinned ? out : c->hio_out.u8();
+        // a page-locked `out` is written by the kernels at its device address; otherwise staged
+        uint8_t *const d_out = host_device_ptr(out);
+        if (!d_out) TE_HIP(c->hio_out.ensure((size_t)h.k * cs));
+        uint8_t *dst = d_out ? d_out : c->hio_out.u8();
         r = decode_enqueue(c, nullptr, c->hio_in.u8(), &it, 1, dst, c->stream, true);
         if (r) return r;
         TE_HIP(hipStreamSynchronize(c->stream));
-        if (!out_pinned) copy_pool(c->device).run({{out, c->hio_out.p, (size_t)h.k * cs}});
+        if (!d_out) copy_pool(c->device).run({{out, c->hio_out.p, (size_t)h.k * cs}});
+        c->dls.direct_out = d_out ? 1u : 0u;
         return TE_OK;
     }
     TE_HIP(c->io_in.ensure(total));
@@ -3567,6 +3620,7 @@ int te_slicer_decode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const 
     if (it.blob_len == 0) return TE_OK;
     if (!out || cap < it.blob_len) return TE_ERR_BUFFER_TOO_SMALL;
     std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     r = ensure_stream(c);
@@ -3586,13 +3640,14 @@ int te_slicer_decode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const 
         for (int i = 0; i < h.n; i++)
             if (slices[i]) segs.push_back({c->hio_in.u8() + (size_t)i * slice_len, slices[i], slice_len});
         copy_pool(c->device).run(segs);
-        const bool out_pinned = host_pinned(out);
-        if (!out_pinned) TE_HIP(c->hio_out.ensure(it.blob_len));
-        uint8_t *dst = out_pinned ? out : c->hio_out.u8();
+        uint8_t *const d_out = host_device_ptr(out);  // page-locked: its device address; else staged
+        if (!d_out) TE_HIP(c->hio_out.ensure(it.blob_len));
+        uint8_t *dst = d_out ? d_out : c->hio_out.u8();
         r = decode_enqueue(c, cfg, c->hio_in.u8(), &it, 1, dst, c->stream, false);
         if (r) return r;
         TE_HIP(hipStreamSynchronize(c->stream));
-        if (!out_pinned) copy_pool(c->device).run({{out, c->hio_out.p, it.blob_len}});
+        if (!d_out) copy_pool(c->device).run({{out, c->hio_out.p, it.blob_len}});
+        c->dls.direct_out = d_out ? 1u : 0u;
         return TE_OK;
     }
     TE_HIP(c->io_in.ensure(total));

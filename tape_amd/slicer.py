@@ -297,6 +297,17 @@ class ClayCoder:
         return {"capacity": cap.value, "used": used.value, "clears": cl.value, "grows": gr.value,
                 "arena_calls": ar.value}
 
+    def decode_launch_stats(self) -> dict:
+        """te_clay_decode_launch_stats: the kernels the handle's last decode or recover call launched --
+        class launches by class id (0..7 decode, 8 + 2*a0 + column recover), their stripes, column
+        groups per workgroup and streams; launches and stripes of the table-driven, generic and
+        pattern kernels; whether a per-call decode stored straight into the caller's buffer."""
+        st = _lib.te_decode_launch_stats()
+        _check(lib.te_clay_decode_launch_stats(self.handle, C.byref(st)), "decode")
+        d = {f: int(getattr(st, f)) for f, _ in st._fields_ if f != "class_launches"}
+        d["class_launches"] = {i: int(v) for i, v in enumerate(st.class_launches) if v}
+        return d
+
     def decode_jit_status(self, timeout_ms: int = 0) -> tuple:
         """(ready, compiling, failed) per-pattern kernels, after waiting up to timeout_ms."""
         v = [C.c_uint32(0) for _ in range(3)]

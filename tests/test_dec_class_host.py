@@ -27,6 +27,30 @@ def test_class_relabelling_every_survivor_set(tmp_path):
     assert "bad 0" in r.stdout and "wrong-class caught 200/200" in r.stdout
 
 
+def test_class_kernels_fit_lds(tmp_path):
+    """dec_class_lds(nslots, nscratch, nring, G) of all 24 classes, G = 1 (the per-call kernels:
+    ring, slot and scratch rows in LDS) and G = 2 (the batch kernels: slot rows), from the row
+    counts the generated kernels register (tests/native/dec_class_lds.cpp): each within the
+    160 KB of LDS a gfx950 workgroup can have.  A class that does not fit would otherwise show
+    only as a launch error on the GPU, and only if its per-call kernel is ever launched.  The
+    figures also may not be smaller than the rows the kernels address: a per-call kernel's ring,
+    slot and scratch rows of 256 bytes, a batch kernel's slot rows of 512."""
+    exe = str(tmp_path / "dec_class_lds")
+    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-I", os.path.join(ROOT, "tape_amd", "csrc"),
+                        os.path.join(ROOT, "tests", "native", "dec_class_lds.cpp"), "-o", exe],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = [list(map(int, line.split())) for line in r.stdout.split("\n") if line.strip()]
+    assert [x[0] for x in rows] == list(range(24))
+    lds_max = 160 * 1024
+    for cid, nslots, nscratch, nring, lds1, lds2 in rows:
+        assert nring >= 1 and nslots >= 1, (cid, nslots, nring)
+        assert (2 * nring + nslots + nscratch) * 256 <= lds1 <= lds_max, (cid, nslots, nscratch, nring, lds1)
+        assert nslots * 512 <= lds2 <= lds_max, (cid, nslots, lds2)
+
+
 def test_class_programs_load_fusion(tmp_path):
     """Row loads per stripe column of every class program after the load fusions
     (tests/native/dec_class_loads.cpp): pinned, so a change that loses the type-1 or in-row pair

@@ -90,7 +90,7 @@ def test_class_recover_batch_all_classes(oracle):
         assert np.array_equal(got[i * g.slice_len:(i + 1) * g.slice_len], exp[i]), (i, objs[i])
 
 
-@pytest.mark.parametrize("a0", [0, 3, 7])
+@pytest.mark.parametrize("a0", range(8))
 def test_class_recover_small_calls(oracle, a0):
     """Per-call recover of one object (one stripe, one class: the class kernel with one wave per
     workgroup), every lost node of both columns."""
@@ -102,3 +102,26 @@ def test_class_recover_small_calls(oracle, a0):
     keep = _survivors(rnd, a0)
     for lost in [j for j in range(N) if j not in keep]:
         assert batch.reconstruct(T.Slicer.clay_default(), lost, [(i, sl[i]) for i in keep]) == sl[lost], lost
+
+
+@pytest.mark.parametrize("a0", range(8))
+def test_class_recover_small_calls_1mb_stripe(oracle, a0):
+    """The same on 1 MB stripes (sub-chunk 1430: the per-call recover kernels over six 64-word
+    column groups, the last one partial), a lost node of each column; the launch stats show the
+    per-call kernel of the expected class."""
+    from tape_amd import batch
+    # the smallest object with 1 MB stripes: a full stripe and a second one holding one byte
+    data = oracle.splitmix64_bytes(0x1B + a0, 1_000_001).tobytes()
+    s = T.Slicer.clay_default()
+    assert s.geometry(len(data)).sub_chunk_size == 1430
+    sl = s.encode(data)
+    rnd = random.Random(a0 + 80)
+    keep = _survivors(rnd, a0)
+    for yl in (0, 1):
+        lost = rnd.choice([j for j in range(10 * yl, 10 * yl + 10) if j not in keep])
+        r = T.Slicer.clay_default()
+        assert batch.reconstruct(r, lost, [(i, sl[i]) for i in keep]) == sl[lost], lost
+        st = r.coder.decode_launch_stats()
+        assert st["class_g"] == 1 and st["class_stripes"] == 2, st
+        assert st["class_launches"].get(8 + 2 * a0 + yl) == 1, st  # stripe 0 is not rotated
+        assert (st["table_stripes"], st["generic_stripes"], st["jit_stripes"]) == (0, 0, 0), st

@@ -177,6 +177,23 @@ def test_kernel_timing_api_without_device():
     assert lib.te_kernel_timing(0) == 0
 
 
+def test_decode_launch_stats_before_any_call():
+    """te_clay_decode_launch_stats is host bookkeeping: all zero on a fresh handle, no device needed,
+    null arguments refused; the ctypes mirror has the C struct's size (24 + 6 32-bit and 4 64-bit
+    fields, no padding)."""
+    assert C.sizeof(_lib.te_decode_launch_stats) == 24 * 4 + 8 + 6 * 4 + 3 * 8
+    c = T.ClayCoder(20, 7, 16)
+    st = _lib.te_decode_launch_stats()
+    C.memset(C.byref(st), 0xFF, C.sizeof(st))
+    assert _lib.lib.te_clay_decode_launch_stats(c.handle, C.byref(st)) == 0
+    assert bytes(st) == bytes(C.sizeof(st))
+    assert c.decode_launch_stats() == {"class_launches": {}, "class_stripes": 0, "class_g": 0, "class_streams": 0,
+                                       "table_launches": 0, "generic_launches": 0, "jit_launches": 0, "direct_out": 0,
+                                       "table_stripes": 0, "generic_stripes": 0, "jit_stripes": 0}
+    assert _lib.lib.te_clay_decode_launch_stats(None, C.byref(st)) == _lib.TE_ERR_INVALID_ARG
+    assert _lib.lib.te_clay_decode_launch_stats(c.handle, None) == _lib.TE_ERR_INVALID_ARG
+
+
 def test_recover_needs_device():
     import ctypes as C
     from tape_amd import _lib
