@@ -127,7 +127,8 @@ int te_clay_decode_store_stats(te_clay *c, uint32_t *capacity, uint32_t *used, u
                                uint64_t *arena_calls);
 /* Which kernels the handle's last decode call launched (diagnostics; host bookkeeping only, no
  * effect on results): one te_clay_decode / te_slicer_decode / te_decode_batch_device /
- * te_recover_batch_device call, summed over its parts and windows when a recover batch is split.
+ * te_recover_batch_device call (or the decode part of their verified forms), summed over its parts
+ * and windows when a recover batch is split.
  * Zeroed when such a call has passed its argument checks and starts its device work; all zero
  * before the first one.  class_g is that of the call's last class launches, class_streams the
  * most streams any part used. */
@@ -436,6 +437,87 @@ int te_merkle_verify_leaf_hash(const uint8_t leaf_hash[TE_HASH_SIZE], const uint
 int te_commit_batch_device(const uint8_t *d_slices, uint64_t obj_stride, uint64_t slice_len, uint32_t n,
                            size_t nobj, uint32_t height, uint8_t *d_leaf_hashes, uint8_t *d_roots,
                            uint8_t *d_proofs, void *hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Verified reads: the read side of the commitments.  Every reader of the reference checks a
+ * slice against the object's leaves (BlobEncoding::leaves) before or after it touches the codec:
+ * the gateway's object read (network/gateway/src/http/handlers/object/decode.rs:121-139), node
+ * recover (network/node/src/features/spool/recover.rs:207-218), repair (repair.rs:339-341), sync
+ * (sync.rs:266-289) and snapshot (network/protocol/src/snapshot.rs:255).
+ * ------------------------------------------------------------------------------------------ */
+/* BlobEncoding::verify_slice (lib/core/src/track/blob.rs:72-79): 1 if position < n and
+ * hash_leaf(data) == leaves[position] (leaves: n * 32 bytes), else 0.  Any length.  Host. */
+int te_verify_slice(const uint8_t *leaves, uint32_t n, uint32_t position, const uint8_t *data, size_t len);
+
+typedef struct te_verify_item {
+    uint64_t offset;     /* the slice's bytes at d_data + offset; offset % 4 == 0 */
+    uint64_t len;        /* len % 4 == 0; 0 is hash_leaf(&[]) */
+    uint32_t expected;   /* its leaf hash at d_expected + expected * 32 */
+    uint32_t object;     /* on a match, d_good_mask[object] |= bit */
+    uint32_t bit;
+    uint32_t pad_;
+} te_verify_item;
+/* Host only: the order in which the leaf-verify kernel walks `items`, by SHA-256 block count,
+ * descending (equal counts keep the caller's order), so that the lanes of a wave hash slices of
+ * like length: order[j] = the caller's index of the j-th item walked. */
+int te_verify_order(const te_verify_item *items, size_t nitems, uint32_t *order);
+/* hash_leaf of nitems slices of any lengths on the device, checked against expected hashes: the
+ * batch form of verify_slice for slices in HBM (DEVICE pointers, `items` a host array; enqueued on
+ * hip_stream, returns without waiting).  Outputs are indexed as `items` is:
+ *   d_digests   nitems * 32 bytes, required: hash_leaf of item i at d_digests + i * 32 (the call
+ *               also parks each slice's running state there between its kernel launches);
+ *   d_ok        nitems uint32, or NULL: 1 if item i's digest equals its expected hash, else 0;
+ *   d_good_mask uint32 per object, or NULL: a matching item ORs its `bit` into d_good_mask[object].
+ *               The call only ever sets bits: the caller zeroes the masks first.
+ * d_expected NULL: digests only (d_ok and d_good_mask are then not written).
+ * A len or an offset that is no multiple of 4 is TE_ERR_INVALID_ARG, as in te_commit_batch_device. */
+int te_verify_leaves_device(te_clay *c, const uint8_t *d_data, const te_verify_item *items, size_t nitems,
+                            const uint8_t *d_expected, uint8_t *d_digests, uint32_t *d_ok, uint32_t *d_good_mask,
+                            void *hip_stream);
+/* The gateway's object read (decode.rs:121-139) over a batch: te_decode_batch_device in which a
+ * slice enters the decode only if hash_leaf(slice) == leaves[position].  h_leaves: nobj * n * 32
+ * bytes (host), each object's BlobEncoding::leaves.  Every present slice is verified;
+ * h_rejected_mask[o] (or NULL) = the present slices that failed (avail & ~good, the handler's
+ * hash_mismatches).  An object with at least k verified slices decodes from them, h_status[o] =
+ * TE_OK; any other gets h_status[o] = TE_ERR_NOT_ENOUGH_SLICES ("insufficient verified slices",
+ * decode.rs:160-170) and nothing is written to its output range.  Returns TE_OK if the call ran;
+ * per-object outcomes are in h_status (nobj ints, required).
+ * The survivor set of each object is chosen on the host from the verified masks, so the call WAITS
+ * ONCE on hip_stream, between the verify kernel and the decode; the decode itself is enqueued and
+ * not waited for.  A caller who wants to overlap that wait with other work calls
+ * te_verify_leaves_device and te_decode_batch_device on streams of their own.
+ * slice_len % 4 == 0 and slices_off % 4 == 0 (TE_ERR_INVALID_ARG otherwise). */
+int te_decode_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                    const te_decode_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                    size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, int *h_status,
+                                    void *hip_stream);
+/* Node recover with both of its checks (recover.rs:207-218): te_recover_batch_device from the peer
+ * slices that verify against h_leaves (as te_decode_verified_batch_device: h_rejected_mask,
+ * h_status, one wait), then verify_slice(lost, rebuilt) on the device: h_ok[o] = 1 if the rebuilt
+ * slice hashes to leaves[lost], else 0 (0 too for an object that was not rebuilt).  The rebuilt
+ * bytes are written either way; the caller discards a slice whose h_ok is 0 (recover.rs:216).
+ * Waits for the results (h_ok is host memory).  out_off % 4 == 0. */
+int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                     const te_recover_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                     size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, uint32_t *h_ok,
+                                     int *h_status, void *hip_stream);
+/* Repair with its check (repair.rs:339-341): te_repair_batch_device, then verify_slice(plan.lost,
+ * repaired) on the device into h_ok[o].  Helper fragments have no leaf of their own, so only the
+ * result is checked.  h_leaves: nobj * n * 32 bytes.  The repaired bytes are written either way.
+ * Waits for the results.  out_off % 4 == 0 and a repaired length that is a multiple of 4. */
+int te_repair_verified_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair_object *objs,
+                                    const uint8_t *h_leaves, size_t nobj, uint8_t *d_out, uint32_t *h_ok,
+                                    void *hip_stream);
+/* The per-call form for host slices: Slicer::decode (slicer.rs:298-364) behind the gateway's check
+ * (decode.rs:121-139).  slices[i] == NULL marks slice i missing; leaves: n * 32 bytes.  Slices
+ * whose hash_leaf differs from leaves[i] are left out of the decode and reported in
+ * *rejected_mask (or NULL); fewer than k verified slices is TE_ERR_NOT_ENOUGH_SLICES.  The leaf
+ * hashes follow te_set_commit_hashing: the host pool's SHA-256 (te_hash_leaves) or the leaf-verify
+ * kernel over the uploaded slices (TE_HASH_AUTO: the host for the few slices of one call; the
+ * device needs slice_len % 4 == 0 and the host hashes otherwise).  The results are identical. */
+int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
+                              const uint8_t *leaves, uint8_t *out, size_t cap, size_t *out_len,
+                              uint32_t *rejected_mask);
 
 /* ------------------------------------------------------------------------------------------
  * OuterCoder (lib/slicer/src/outer.rs:19-197): single-level Reed-Solomon over

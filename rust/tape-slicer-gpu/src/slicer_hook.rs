@@ -72,6 +72,35 @@ impl ObjectCoder for ClayCoder {
     }
 }
 
+impl ClayCoder {
+    /// The gateway's object read (network/gateway/src/http/handlers/object/decode.rs:121-139) in one
+    /// te_slicer_decode_verified: a slice enters the decode only if hash_leaf(slice) ==
+    /// leaves[index] (BlobEncoding::verify_slice, lib/core/src/track/blob.rs:72-79).  Returns the
+    /// object and the mask of rejected slices (the handler's hash_mismatches); fewer than k verified
+    /// slices is NotEnoughSlices.
+    pub fn decode_object_verified(&mut self, cfg: &ObjectCfg, slices: &[(usize, &[u8])], leaves: &[[u8; 32]])
+                                  -> Result<(Vec<u8>, u32), DecodeError> {
+        if slices.is_empty() || leaves.len() != self.n() { return Err(DecodeError::NotEnoughSlices) }
+        let slen = slices[0].1.len();
+        let mut ptrs = vec![std::ptr::null::<u8>(); self.n()];
+        for (i, s) in slices {
+            if *i >= self.n() || s.len() != slen { return Err(DecodeError::InvalidLayout) }
+            ptrs[*i] = s.as_ptr();
+        }
+        let mut out = vec![0u8; slen.saturating_sub(ffi::TE_META_SIZE as usize) * self.k + 1];
+        let (mut got, mut rejected) = (0usize, 0u32);
+        let c = cfg.ffi();
+        let r = unsafe {
+            ffi::te_slicer_decode_verified(self.raw.as_ptr(), &c, ptrs.as_ptr(), slen, leaves.as_ptr() as *const u8,
+                                           out.as_mut_ptr(), out.len(), &mut got, &mut rejected)
+        };
+        decode_status(r).map(|_| {
+            out.truncate(got);
+            (out, rejected)
+        })
+    }
+}
+
 /// RepairPlan (repair.rs:16-28) with the reference's public fields, read back from the library's
 /// plan when it is built, so callers that walk `plan.stripes` (the node's per_helper_reqs,
 /// network/node/src/features/spool/repair.rs:468-491) read it unchanged; the library handle it was

@@ -78,6 +78,11 @@ class te_repair_object(C.Structure):
                 ("metadata", C.c_uint8 * 48)]
 
 
+class te_verify_item(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("len", C.c_uint64), ("expected", C.c_uint32), ("object", C.c_uint32),
+                ("bit", C.c_uint32), ("pad_", C.c_uint32)]
+
+
 DECODE_CLASSES = 24  # TE_DECODE_CLASSES
 
 
@@ -189,6 +194,15 @@ def _load() -> C.CDLL:
         "te_merkle_proof_from_leaf_hashes": (i, [u8p, sz, sz, u32, u8p]),
         "te_merkle_verify_leaf_hash": (i, [u8p, u8p, u8p, sz, u64, u32]),
         "te_commit_batch_device": (i, [vp, u64, u64, u32, sz, u32, vp, vp, vp, vp]),
+        "te_verify_slice": (i, [u8p, u32, u32, u8p, sz]),
+        "te_verify_order": (i, [C.POINTER(te_verify_item), sz, u32p]),
+        "te_verify_leaves_device": (i, [vp, vp, C.POINTER(te_verify_item), sz, vp, vp, vp, vp, vp]),
+        "te_decode_verified_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_decode_object), u8p,
+                                                u8p, sz, vp, u32p, C.POINTER(i), vp]),
+        "te_recover_verified_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_object), u8p,
+                                                 u8p, sz, vp, u32p, u32p, C.POINTER(i), vp]),
+        "te_repair_verified_batch_device": (i, [vp, vp, C.POINTER(te_repair_object), u8p, sz, vp, u32p, vp]),
+        "te_slicer_decode_verified": (i, [vp, C.POINTER(te_slicer_cfg), pp, sz, u8p, u8p, sz, szp, u32p]),
         "te_outer_chunk_bytes": (sz, [u32, sz]),
         "te_outer_encode": (i, [u32, u32, u8p, sz, u8p, sz, szp]),
         "te_outer_decode": (i, [u32, u32, pp, sz, u8p, sz]),

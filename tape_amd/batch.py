@@ -210,6 +210,55 @@ def recover_batch(slicer: Slicer, slices, objs: list[tuple[int, int, int, int, i
     _check(r, "recover")
 
 
+def _leaf_bytes(leaves, nobj: int, n: int):
+    """nobj * n * 32 bytes of leaves (bytes, or a list per object of n 32-byte hashes) as a ctypes array."""
+    b = bytes(leaves) if isinstance(leaves, (bytes, bytearray, memoryview)) else \
+        b"".join(bytes(h) for obj in leaves for h in obj)
+    if len(b) != nobj * n * 32:
+        raise ValueError(f"leaves: {len(b)} bytes, expected {nobj} x {n} x 32")
+    return (C.c_uint8 * max(1, len(b))).from_buffer_copy(b or b"\0")
+
+
+def decode_verified_batch(slicer: Slicer, slices, objs, metas: bytes, leaves, out, stream=None):
+    """te_decode_verified_batch_device: the gateway's object read (decode.rs:121-139) over a batch.
+    objs / metas as for decode_batch; leaves: each object's n leaf hashes (BlobEncoding::leaves).
+    A slice enters the decode only if hash_leaf(slice) == leaves[position].  Returns (status,
+    rejected): per object TE_OK or TE_ERR_NOT_ENOUGH_SLICES (its output range is then untouched),
+    and the mask of present slices that failed.  Waits once on the stream for the verify kernel; the
+    decode is enqueued."""
+    arr = objs if _is_desc(objs) else decode_descs(objs)
+    cfg = slicer._cfg()
+    nobj = len(arr)
+    mb = (C.c_uint8 * max(1, len(metas))).from_buffer_copy(metas if metas else b"\0")
+    lb = _leaf_bytes(leaves, nobj, slicer.coder.n())
+    rej = (C.c_uint32 * max(1, nobj))()
+    st = (C.c_int * max(1, nobj))()
+    r = lib.te_decode_verified_batch_device(slicer.coder.handle, C.byref(cfg), C.c_void_p(slices.data_ptr()), arr, mb,
+                                            lb, nobj, C.c_void_p(out.data_ptr()), rej, st, _stream_ptr(stream))
+    _check(r, "decode")
+    return [int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]]
+
+
+def recover_verified_batch(slicer: Slicer, slices, objs: list[tuple[int, int, int, int, int]], metas: bytes, leaves,
+                           out, stream=None):
+    """te_recover_verified_batch_device: node recover with both checks of recover.rs:207-218 --
+    peers verified before the rebuild, the rebuilt slice against leaves[lost] after.  objs as for
+    recover_batch.  Returns (status, rejected, ok) per object; the rebuilt bytes are written whether
+    ok or not.  Waits for the results."""
+    arr = (_lib.te_recover_object * max(1, len(objs)))(*[_lib.te_recover_object(*o) for o in objs])
+    cfg = slicer._cfg()
+    nobj = len(objs)
+    mb = (C.c_uint8 * max(1, len(metas))).from_buffer_copy(metas if metas else b"\0")
+    lb = _leaf_bytes(leaves, nobj, slicer.coder.n())
+    rej = (C.c_uint32 * max(1, nobj))()
+    ok = (C.c_uint32 * max(1, nobj))()
+    st = (C.c_int * max(1, nobj))()
+    r = lib.te_recover_verified_batch_device(slicer.coder.handle, C.byref(cfg), C.c_void_p(slices.data_ptr()), arr, mb,
+                                             lb, nobj, C.c_void_p(out.data_ptr()), rej, ok, st, _stream_ptr(stream))
+    _check(r, "recover")
+    return [int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]], [int(x) for x in ok[:nobj]]
+
+
 def reconstruct(slicer: Slicer, lost: int, peer_slices: list[tuple[int, bytes]]) -> bytes:
     """recover.rs:411-442 `reconstruct`: decode the peers' slices, re-encode, return slice `lost`
     (one object, host bytes in and out, through recover_batch)."""
@@ -258,3 +307,17 @@ def repair_batch(coder: ClayCoder, helpers, objs, out, stream=None) -> None:
     r = lib.te_repair_batch_device(coder.handle, C.c_void_p(helpers.data_ptr()), arr, len(arr),
                                    C.c_void_p(out.data_ptr()), _stream_ptr(stream))
     _check(r, "repair")
+
+
+def repair_verified_batch(coder: ClayCoder, helpers, objs, leaves, out, stream=None) -> list[int]:
+    """te_repair_verified_batch_device: repair_batch, then the repaired slice against
+    leaves[plan.lost] on the device (repair.rs:339-341).  Returns ok per object; the repaired bytes
+    are written either way.  Waits for the results."""
+    arr = objs if _is_desc(objs) else repair_descs(objs)
+    nobj = len(arr)
+    lb = _leaf_bytes(leaves, nobj, coder.n())
+    ok = (C.c_uint32 * max(1, nobj))()
+    r = lib.te_repair_verified_batch_device(coder.handle, C.c_void_p(helpers.data_ptr()), arr, lb, nobj,
+                                            C.c_void_p(out.data_ptr()), ok, _stream_ptr(stream))
+    _check(r, "repair")
+    return [int(x) for x in ok[:nobj]]

@@ -440,7 +440,11 @@ struct te_clay {
     std::mutex mu;
     int device = 0;                // every allocation and launch of this handle runs on it
     hipStream_t stream = nullptr;  // for the synchronous host-buffer entry points
-    Arena enc, dec, rep, rec;
+    Arena enc, dec, rep, rec, ver;
+    // the verified read calls' workspace (expected hashes, digests, masks) and its page-locked host
+    // side: idle between calls, which wait for their masks before they return
+    DevBuf ver_buf;
+    HostBuf ver_host;
     DevBuf io_in, io_out;          // staging for host-buffer entry points
     HostBuf hio_in, hio_out;       // their page-locked host side (te_slicer_repair's gather / scatter)
     // te_recover_batch_device workspaces (decoded objects, re-encoded slices); `rec_done` is
@@ -552,6 +556,9 @@ static void release_device_state(te_clay *c) {
     c->dec.release();
     c->rep.release();
     c->rec.release();
+    c->ver.release();
+    c->ver_buf.release();
+    c->ver_host.release();
     c->io_in.release();
     c->io_out.release();
     c->hio_in.release();
@@ -4040,6 +4047,332 @@ int te_commit_batch_device(const uint8_t *d_slices, uint64_t obj_stride, uint64_
     KTimer kt(s);
     TE_HIP(launch_commit(a, s));
     kt.stop();
+    return TE_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Verified reads (verify.hip): BlobEncoding::verify_slice (lib/core/src/track/blob.rs:72-79) and
+// its call sites -- the gateway's object read (network/gateway/src/http/handlers/object/
+// decode.rs:121-139), node recover (recover.rs:207-218) and repair (repair.rs:339-341)
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// The kernel's walk order: by block count, descending, equal counts in the caller's order.
+void verify_order(const te_verify_item *items, size_t nitems, std::vector<uint32_t> &order) {
+    order.resize(nitems);
+    for (size_t i = 0; i < nitems; i++) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return verify_blocks(items[x].len) > verify_blocks(items[y].len);
+    });
+}
+
+int verify_check_items(const te_verify_item *items, size_t nitems) {
+    if (nitems > 0xffffffffull || (!items && nitems)) return TE_ERR_INVALID_ARG;
+    for (size_t i = 0; i < nitems; i++)
+        if (items[i].len % 4u || items[i].offset % 4u) return TE_ERR_INVALID_ARG;
+    return TE_OK;
+}
+
+// Handle locked, its device current: the sorted item list through the handle's descriptor arena,
+// then the launches.
+int verify_enqueue(te_clay *c, const uint8_t *d_data, const te_verify_item *items, size_t nitems,
+                   const uint8_t *d_expected, uint8_t *d_digests, uint32_t *d_ok, uint32_t *d_good_mask,
+                   hipStream_t s) {
+    if (nitems == 0) return TE_OK;
+    std::vector<uint32_t> order;
+    verify_order(items, nitems, order);
+    std::vector<VerifyItem> v(nitems);
+    for (size_t j = 0; j < nitems; j++) {
+        const te_verify_item &t = items[order[j]];
+        v[j] = VerifyItem{t.offset, t.len, t.expected, t.object, t.bit, order[j]};
+    }
+    Arena &A = c->ver;
+    A.img.clear();
+    const size_t off = A.put(v.data(), v.size() * sizeof(VerifyItem));
+    int r = A.upload(s);
+    if (r) return r;
+    VerifyArgs a{};
+    a.data = d_data;
+    a.items = A.at<VerifyItem>(off);
+    a.nitems = (uint32_t)nitems;
+    a.expected = d_expected;
+    a.digests = d_digests;
+    a.ok = d_ok;
+    a.good_mask = d_good_mask;
+    KTimer kt(s);
+    TE_HIP(launch_verify(a, v.data(), s));
+    kt.stop();
+    return A.mark_done(s);
+}
+
+// Handle locked, its device current.  Verify `items` (their `expected` index h_expected's nexp
+// hashes, their `object` one of nmask masks) in the handle's workspace and WAIT for the masks:
+// h_good[o] = the bits of object o's matching items.
+int verify_wait(te_clay *c, const uint8_t *d_data, const std::vector<te_verify_item> &items, const uint8_t *h_expected,
+                size_t nexp, size_t nmask, uint32_t *h_good, hipStream_t s) {
+    for (size_t o = 0; o < nmask; o++) h_good[o] = 0;
+    if (items.empty()) return TE_OK;
+    const size_t exp_b = nexp * TE_HASH_SIZE, dig_b = items.size() * TE_HASH_SIZE, mask_b = nmask * sizeof(uint32_t);
+    TE_HIP(c->ver_buf.ensure(exp_b + dig_b + mask_b));
+    TE_HIP(c->ver_host.ensure(exp_b + mask_b));
+    uint8_t *const d = c->ver_buf.as<uint8_t>();
+    uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + exp_b + dig_b);
+    memcpy(c->ver_host.p, h_expected, exp_b);
+    TE_HIP(hipMemcpyAsync(d, c->ver_host.p, exp_b, hipMemcpyHostToDevice, s));
+    TE_HIP(hipMemsetAsync(d_mask, 0, mask_b, s));
+    int r = verify_enqueue(c, d_data, items.data(), items.size(), d, d + exp_b, nullptr, d_mask, s);
+    if (r) return r;
+    TE_HIP(hipMemcpyAsync(c->ver_host.u8() + exp_b, d_mask, mask_b, hipMemcpyDeviceToHost, s));
+    if ((r = sync_sleep(s))) return r;
+    memcpy(h_good, c->ver_host.u8() + exp_b, mask_b);
+    return TE_OK;
+}
+
+inline uint32_t slice_bits(const te_clay *c) { return c->h.n >= 32 ? 0xffffffffu : (1u << c->h.n) - 1u; }
+
+// One verify item per present slice of an object whose slices lie slice_len apart.
+void verify_push_slices(std::vector<te_verify_item> &vi, size_t obj, uint32_t n, uint64_t slices_off, uint64_t slice_len,
+                        uint32_t avail) {
+    for (uint32_t b = 0; b < n; b++)
+        if ((avail >> b) & 1u)
+            vi.push_back(te_verify_item{slices_off + (uint64_t)b * slice_len, slice_len, (uint32_t)(obj * n + b),
+                                        (uint32_t)obj, 1u << b, 0});
+}
+
+}  // namespace
+
+extern "C" {
+
+int te_verify_slice(const uint8_t *leaves, uint32_t n, uint32_t position, const uint8_t *data, size_t len) {
+    if (!leaves || (!data && len) || position >= n) return 0;
+    uint8_t d[TE_HASH_SIZE];
+    hh::hash_leaf(data, len, d);
+    return memcmp(d, leaves + (size_t)position * TE_HASH_SIZE, TE_HASH_SIZE) == 0 ? 1 : 0;
+}
+
+int te_verify_order(const te_verify_item *items, size_t nitems, uint32_t *order) {
+    if ((!items || !order) && nitems) return TE_ERR_INVALID_ARG;
+    if (nitems > 0xffffffffull) return TE_ERR_INVALID_ARG;
+    std::vector<uint32_t> o;
+    verify_order(items, nitems, o);
+    if (nitems) memcpy(order, o.data(), nitems * sizeof(uint32_t));
+    return TE_OK;
+}
+
+int te_verify_leaves_device(te_clay *c, const uint8_t *d_data, const te_verify_item *items, size_t nitems,
+                            const uint8_t *d_expected, uint8_t *d_digests, uint32_t *d_ok, uint32_t *d_good_mask,
+                            void *stream) {
+    if (!c) return TE_ERR_INVALID_ARG;
+    if (nitems == 0) return TE_OK;
+    if (!d_digests) return TE_ERR_INVALID_ARG;
+    int r = verify_check_items(items, nitems);
+    if (r) return r;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    return verify_enqueue(c, d_data, items, nitems, d_expected, d_digests, d_ok, d_good_mask, (hipStream_t)stream);
+}
+
+int te_decode_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                    const te_decode_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                    size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, int *h_status,
+                                    void *stream) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_leaves || !h_status) && nobj)) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    for (size_t i = 0; i < nobj; i++)
+        if (objs[i].slice_len % 4u || objs[i].slices_off % 4u) return TE_ERR_INVALID_ARG;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::vector<DecItem> items(nobj);
+    std::vector<te_verify_item> vi;
+    for (size_t i = 0; i < nobj; i++) {
+        // an object with too few slices to begin with is that object's outcome, not the call's
+        const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, items[i]);
+        if (r && r != TE_ERR_NOT_ENOUGH_SLICES) return r;
+        h_status[i] = r;
+        verify_push_slices(vi, i, n, objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask & all);
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<uint32_t> good(nobj);
+    int r = verify_wait(c, d_slices, vi, h_leaves, nobj * n, nobj, good.data(), s);
+    if (r) return r;
+    std::vector<DecItem> run;
+    for (size_t i = 0; i < nobj; i++) {
+        const uint32_t avail = objs[i].avail_mask & all, ok = avail & good[i];
+        if (h_rejected_mask) h_rejected_mask[i] = avail & ~ok;
+        if (h_status[i]) continue;
+        DecItem it{};
+        if ((h_status[i] = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, ok, it))) continue;
+        it.in_base = objs[i].slices_off;
+        it.out_off = objs[i].out_off;
+        run.push_back(it);
+    }
+    c->dls = te_decode_launch_stats{};
+    if (run.empty()) return TE_OK;
+    return decode_enqueue(c, cfg, d_slices, run.data(), run.size(), d_out, s, false);
+}
+
+int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                     const te_recover_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                     size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, uint32_t *h_ok,
+                                     int *h_status, void *stream) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_leaves || !h_status || !h_ok) && nobj)) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    for (size_t i = 0; i < nobj; i++) {
+        if (objs[i].slice_len % 4u || objs[i].slices_off % 4u || objs[i].out_off % 4u) return TE_ERR_INVALID_ARG;
+        if (objs[i].lost >= n) return TE_ERR_INVALID_SLICE;
+    }
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::vector<te_verify_item> vi;
+    for (size_t i = 0; i < nobj; i++) {
+        DecItem it{};
+        const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, it);
+        if (r && r != TE_ERR_NOT_ENOUGH_SLICES) return r;
+        h_status[i] = r;
+        h_ok[i] = 0;
+        verify_push_slices(vi, i, n, objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask & all);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<uint32_t> good(nobj);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceGuard dg(c->device);
+        TE_HIP(dg.err);
+        const int r = verify_wait(c, d_slices, vi, h_leaves, nobj * n, nobj, good.data(), s);
+        if (r) return r;
+    }
+    // the objects with k verified peers, rebuilt from those (the handle is locked by the call)
+    std::vector<te_recover_object> run;
+    std::vector<uint8_t> run_meta;
+    std::vector<size_t> run_of;
+    for (size_t i = 0; i < nobj; i++) {
+        const uint32_t avail = objs[i].avail_mask & all, ok = avail & good[i];
+        if (h_rejected_mask) h_rejected_mask[i] = avail & ~ok;
+        if (h_status[i]) continue;
+        DecItem it{};
+        if ((h_status[i] = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, ok, it))) continue;
+        te_recover_object o = objs[i];
+        o.avail_mask = ok;
+        run.push_back(o);
+        run_meta.insert(run_meta.end(), h_meta + i * TE_META_SIZE, h_meta + (i + 1) * TE_META_SIZE);
+        run_of.push_back(i);
+    }
+    if (run.empty()) return TE_OK;
+    int r = recover_batch(c, cfg, d_slices, run.data(), run_meta.data(), run.size(), d_out, stream, false);
+    if (r) return r;
+    vi.clear();
+    for (size_t i : run_of)
+        vi.push_back(te_verify_item{objs[i].out_off, objs[i].slice_len, (uint32_t)(i * n + objs[i].lost), (uint32_t)i, 1u, 0});
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    if ((r = verify_wait(c, d_out, vi, h_leaves, nobj * n, nobj, good.data(), s))) return r;
+    for (size_t i : run_of) h_ok[i] = good[i] & 1u;
+    return TE_OK;
+}
+
+int te_repair_verified_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair_object *objs,
+                                    const uint8_t *h_leaves, size_t nobj, uint8_t *d_out, uint32_t *h_ok,
+                                    void *stream) {
+    if (!c || ((!objs || !h_leaves || !h_ok) && nobj)) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n;
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    std::vector<te_verify_item> vi;
+    for (size_t i = 0; i < nobj; i++) {
+        const te_repair_plan *p = objs[i].plan;
+        if (!p || p->n != n || p->lost >= n) return TE_ERR_INVALID_ARG;
+        const uint64_t len = (uint64_t)p->ns * p->cs + TE_META_SIZE;
+        if (len % 4u || objs[i].out_off % 4u) return TE_ERR_INVALID_ARG;
+        vi.push_back(te_verify_item{objs[i].out_off, len, (uint32_t)(i * n + p->lost), (uint32_t)i, 1u, 0});
+    }
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    int r = te_repair_batch_device(c, d_helpers, objs, nobj, d_out, stream);
+    if (r) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    std::vector<uint32_t> good(nobj);
+    if ((r = verify_wait(c, d_out, vi, h_leaves, nobj * n, nobj, good.data(), (hipStream_t)stream))) return r;
+    for (size_t i = 0; i < nobj; i++) h_ok[i] = good[i] & 1u;
+    return TE_OK;
+}
+
+int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
+                              const uint8_t *leaves, uint8_t *out, size_t cap, size_t *out_len,
+                              uint32_t *rejected_mask) {
+    if (!c || !cfg || !slices || !leaves) return TE_ERR_INVALID_ARG;
+    const ClayHost &h = c->h;
+    const int n = h.n;
+    uint32_t avail = 0, good = 0;
+    for (int i = 0; i < n; i++)
+        if (slices[i]) avail |= 1u << i;
+    if (!avail) return TE_ERR_NOT_ENOUGH_SLICES;
+    if (slice_len < TE_META_SIZE) return TE_ERR_INVALID_LAYOUT;
+    // one call's 7..20 slices: a host core with the SHA extensions hashes a slice about as fast as
+    // it crosses PCIe, a device lane at ~24 MB/s, so TE_HASH_AUTO is the host
+    const bool device = g_commit_hashing.load() == TE_HASH_DEVICE && slice_len % 4u == 0;
+    auto finish = [&](uint32_t ok) {
+        if (rejected_mask) *rejected_mask = avail & ~ok;
+        return __builtin_popcount(ok) < h.k ? (int)TE_ERR_NOT_ENOUGH_SLICES : (int)TE_OK;
+    };
+    if (!device) {
+        // te_hash_leaves' interleaved lanes over the present slices, on the calling thread
+        const int lanes = hh::Pool::get().lanes();
+        uint8_t dig[64][TE_HASH_SIZE];
+        int idx[64], m = 0;
+        for (int i = 0; i < n; i++)
+            if (slices[i]) idx[m++] = i;
+        for (int j0 = 0; j0 < m; j0 += lanes) {
+            const int L = std::min(lanes, m - j0);
+            const uint8_t *src[hh::kMaxLanes];
+            uint8_t *dst[hh::kMaxLanes];
+            for (int l = 0; l < L; l++) {
+                src[l] = slices[idx[j0 + l]];
+                dst[l] = dig[j0 + l];
+            }
+            hh::hash_leaves(L, src, slice_len, dst);
+        }
+        for (int j = 0; j < m; j++)
+            if (memcmp(dig[j], leaves + (size_t)idx[j] * TE_HASH_SIZE, TE_HASH_SIZE) == 0) good |= 1u << idx[j];
+        int r = finish(good);
+        if (r) return r;
+        const uint8_t *kept[64];
+        for (int i = 0; i < n; i++) kept[i] = ((good >> i) & 1u) ? slices[i] : nullptr;
+        return te_slicer_decode(c, cfg, kept, slice_len, out, cap, out_len);
+    }
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    int r = ensure_stream(c);
+    if (r) return r;
+    // the slices go up once: the kernel hashes them in the staging the decode then reads
+    TE_HIP(c->io_in.ensure((size_t)n * slice_len));
+    if ((r = upload_slices(c, slices, slice_len))) return r;
+    std::vector<te_verify_item> vi;
+    verify_push_slices(vi, 0, (uint32_t)n, 0, slice_len, avail);
+    if ((r = verify_wait(c, c->io_in.as<uint8_t>(), vi, leaves, (size_t)n, 1, &good, c->stream))) return r;
+    if ((r = finish(good))) return r;
+    const int first = __builtin_ctz(good);  // the layout comes from a verified slice
+    DecItem it{};
+    if ((r = decode_validate(c, slices[first] + slice_len - TE_META_SIZE, slice_len, good, it))) return r;
+    if (out_len) *out_len = it.blob_len;
+    if (it.blob_len == 0) return TE_OK;
+    if (!out || cap < it.blob_len) return TE_ERR_BUFFER_TOO_SMALL;
+    it.in_base = 0;
+    it.out_off = 0;
+    TE_HIP(c->io_out.ensure(it.blob_len));
+    if ((r = decode_enqueue(c, cfg, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, false))) return r;
+    TE_HIP(hipMemcpyAsync(out, c->io_out.p, it.blob_len, hipMemcpyDeviceToHost, c->stream));
+    TE_HIP(hipStreamSynchronize(c->stream));
     return TE_OK;
 }
 

@@ -313,6 +313,31 @@ struct CommitArgs {
 };
 hipError_t launch_commit(const CommitArgs &a, hipStream_t s);
 
+// ---- leaf verification (verify.hip) ----
+// One slice to hash and check, in the order the kernel walks them: sorted by block count,
+// descending.  `index` is the item's position in the caller's list; digests and ok are stored there.
+struct VerifyItem {
+    uint64_t offset;    // slice bytes at data + offset (4-aligned)
+    uint64_t len;       // % 4 == 0; 0 is hash_leaf(&[])
+    uint32_t expected;  // its leaf at expected + 32 * this
+    uint32_t object;    // on a match: good_mask[object] |= bit
+    uint32_t bit;
+    uint32_t index;
+};
+struct VerifyArgs {
+    const uint8_t *data;
+    const VerifyItem *items;
+    uint32_t nitems;
+    const uint8_t *expected;  // or null: digests only
+    uint8_t *digests;         // nitems * 32: a lane's state between launches, then its digest
+    uint32_t *ok;             // nitems, or null
+    uint32_t *good_mask;      // or null; only ever OR-ed into
+};
+constexpr uint64_t kVerifyBlocksPerLaunch = 1536;  // = commit.hip's kLeafBlocksPerLaunch
+// SHA-256 blocks of hash_leaf over len bytes: "LEAF", the bytes, 0x80, zeros, the 8-byte length
+__host__ __device__ inline uint64_t verify_blocks(uint64_t len) { return (len + 4u + 8u) / 64u + 1u; }
+hipError_t launch_verify(const VerifyArgs &a, const VerifyItem *h_items, hipStream_t s);
+
 hipError_t launch_encode_rows(int k, bool masked, const EncArgs &a, hipStream_t s);
 // encode_dma.hip: Clay(20,7,16), 1,280 < sub-chunk <= 1,440 bytes (the 1 MB stripes), no scratch
 bool encode_dma_supported(int n, int k, uint32_t sc);

@@ -110,6 +110,48 @@ def verify_proof(data: bytes, root: bytes, proof, index: int, height: int = SLIC
     return verify_leaf_hash(hash_leaf(data), root, proof, index, height)
 
 
+def verify_slice(leaves, position: int, data: bytes) -> bool:
+    """BlobEncoding::verify_slice (lib/core/src/track/blob.rs:72-79): position < len(leaves) and
+    hash_leaf(data) == leaves[position].  Host."""
+    b = bytes(data)
+    buf = (C.c_uint8 * max(1, len(b))).from_buffer_copy(b or b"\0")
+    if position < 0:
+        return False
+    return lib.te_verify_slice(_hashes(leaves), len(leaves), position, buf, len(b)) == 1
+
+
+def verify_items(items):
+    """Prepared te_verify_item array (build once, reuse): (offset, len, expected hash index, object,
+    bit) per slice."""
+    if hasattr(items, "_length_"):
+        return items
+    return (_lib.te_verify_item * len(items))(*[_lib.te_verify_item(o, ln, e, ob, bit, 0)
+                                                for o, ln, e, ob, bit in items])
+
+
+def verify_order(items) -> list[int]:
+    """te_verify_order: the caller's indices in the order the leaf-verify kernel walks them (by
+    SHA-256 block count, descending).  Host."""
+    arr = verify_items(items)
+    out = (C.c_uint32 * max(1, len(items)))()
+    _check(lib.te_verify_order(arr, len(items), out))
+    return [int(x) for x in out[:len(items)]]
+
+
+def verify_leaves_device(coder, data, items, expected, digests, ok=None, good_mask=None, stream=None) -> None:
+    """te_verify_leaves_device: hash_leaf of ragged slices in a uint8 cuda tensor, checked against
+    expected hashes.  items: (offset, len, expected hash index, object, bit) per slice, or
+    verify_items(...) of them; expected
+    (uint8 cuda, 32 bytes per hash, or None for digests only); digests (uint8 cuda, 32 per item);
+    ok / good_mask (int32 cuda tensors or None; good_mask is OR-ed into, zero it first).  Enqueued
+    on the stream."""
+    from .batch import _stream_ptr
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+    arr = verify_items(items)
+    _check(lib.te_verify_leaves_device(coder.handle, ptr(data), arr, len(items), ptr(expected), ptr(digests), ptr(ok),
+                                       ptr(good_mask), _stream_ptr(stream)))
+
+
 def commit_batch(slices, obj_stride: int, slice_len: int, n: int, nobj: int, leaf_hashes, roots=None,
                  proofs=None, height: int = SLICE_TREE_HEIGHT, stream=None) -> None:
     """Device batch (te_commit_batch_device): uint8 cuda tensors; object o's slice i at

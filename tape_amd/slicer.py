@@ -587,6 +587,36 @@ class Slicer:
         _check(r, "decode")
         return bytes(out)[:got.value]
 
+    def decode_verified(self, chunks: list[tuple[int, bytes]], leaves) -> tuple[bytes, list[int]]:
+        """Slicer::decode behind the gateway's check (network/gateway/src/http/handlers/object/
+        decode.rs:121-139): a slice enters the decode only if hash_leaf(slice) == leaves[index].
+        Returns (object bytes, indices of the rejected slices); fewer than k verified slices raise
+        DecodeError("NotEnoughSlices").  Hashed on the host or the device (set_commit_hashing)."""
+        if not chunks:
+            raise DecodeError("NotEnoughSlices")
+        n = self.n()
+        if len(leaves) != n:
+            raise ValueError(f"{n} leaf hashes expected")
+        slice_len = len(chunks[0][1])
+        ptrs = (C.c_void_p * n)()
+        keep = []
+        for idx, data in chunks:
+            if not (0 <= idx < n) or len(data) != slice_len:
+                raise DecodeError("InvalidLayout")
+            b = _buf(data)
+            keep.append(b)
+            ptrs[idx] = C.cast(b, C.c_void_p)
+        # the object is at most the slices' payload (k data chunks per stripe)
+        out = (C.c_uint8 * max(1, n * slice_len))()
+        got = C.c_size_t()
+        rej = C.c_uint32()
+        cfg = self._cfg()
+        r = lib.te_slicer_decode_verified(self.coder.handle, C.byref(cfg), ptrs, slice_len,
+                                          _buf(b"".join(bytes(h) for h in leaves)), out, len(out), C.byref(got),
+                                          C.byref(rej))
+        _check(r, "decode")
+        return bytes(out)[:got.value], [i for i in range(n) if rej.value >> i & 1]
+
     # repair.rs:137-367
     def repair_plan_from_params(self, lost: int, available: list[int], blob_len: int, stripe_size: int) -> RepairPlan:
         av = (C.c_uint32 * max(1, len(available)))(*available)
