@@ -146,6 +146,42 @@ typedef struct te_decode_launch_stats {
     uint64_t table_stripes, generic_stripes, jit_stripes;
 } te_decode_launch_stats;
 int te_clay_decode_launch_stats(te_clay *c, te_decode_launch_stats *out);
+/* Which kernels the handle's last encode call launched (diagnostics; host bookkeeping only, no
+ * effect on results): one te_clay_encode / te_slicer_encode / te_encode_batch_device /
+ * te_encode_batch_host / te_encode_commit_batch_host / te_stream_submit call, or the re-encode of
+ * the parity-lost stripes in a te_recover_batch_device call (and its verified form), summed over
+ * its windows and launch groups.  A launch group is the stripes of one (chunk size, slice length,
+ * data end dword aligned or not, source address even or odd).
+ * Zeroed when such a call has passed its argument checks and starts its device work; all zero
+ * before the first one.  stage_g and stage_wgs are those of the call's last staged launch. */
+typedef struct te_encode_launch_stats {
+    uint32_t dma_launches;       /* LDS-DMA kernel (1 MB stripes of Clay(20,7,16)): every launch */
+    uint32_t dma_level1_launches, dma_level2_launches; /* of those, the halves of split launches:
+                                    the level-1 plane rows, then the level-2 chain */
+    uint32_t stage_launches;     /* staged kernel (Clay(20,7,16) and (20,10,19), even addresses) */
+    uint32_t stage_masked_launches; /* of those, with a data end that is not dword aligned */
+    uint32_t stage_g;            /* their waves (64-word column groups) per workgroup, 1..6 (0: no
+                                    staged launch) */
+    uint32_t stage_wgs;          /* their workgroups per stripe */
+    uint32_t generic_launches;   /* generic kernel: other profiles, odd source addresses, slices
+                                    past the 31-bit offset limit */
+    uint64_t dma_stripes, stage_stripes, generic_stripes; /* a split launch's stripes count once */
+} te_encode_launch_stats;
+int te_clay_encode_launch_stats(te_clay *c, te_encode_launch_stats *out);
+/* The same for the handle's last repair call: one te_clay_repair / te_slicer_repair /
+ * te_repair_batch_device / te_repair_verified_batch_device call, summed over its chunk sizes.
+ * fold_g, fold_wgs, stage_g and stage_wgs are those of the call's last such launch. */
+typedef struct te_repair_launch_stats {
+    uint32_t fold_launches;      /* folded kernel: Clay(20,7,16), all 19 others up or one of the
+                                    other column's first 7 down, sub-chunk >= 8 */
+    uint32_t stage_launches;     /* staged kernel: every other helper set with a plane program */
+    uint32_t generic_launches;   /* generic kernel: sub-chunk < 8, or a set without a program */
+    uint32_t fold_g, fold_wgs;   /* waves per workgroup and workgroups per stripe (0: no launch) */
+    uint32_t stage_g, stage_wgs;
+    uint32_t pad_;
+    uint64_t fold_stripes, stage_stripes, generic_stripes;
+} te_repair_launch_stats;
+int te_clay_repair_launch_stats(te_clay *c, te_repair_launch_stats *out);
 int te_clay_get_info(const te_clay *c, te_clay_info *out);
 /* ClayCoder::chunk_size_for  clay.rs:61-73 */
 size_t te_clay_chunk_size_for(const te_clay *c, size_t input_len);

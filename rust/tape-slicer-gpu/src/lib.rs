@@ -243,6 +243,22 @@ impl ClayCoder {
         if s != 0 { fatal(s) }
         unsafe { st.assume_init() }
     }
+    /// The kernels the last encode call on this coder launched (LDS-DMA, staged and generic launches
+    /// and stripes, the staged launches' waves per workgroup and workgroups per stripe).
+    pub fn encode_launch_stats(&self) -> ffi::te_encode_launch_stats {
+        let mut st = std::mem::MaybeUninit::<ffi::te_encode_launch_stats>::zeroed();
+        let s = unsafe { ffi::te_clay_encode_launch_stats(self.raw.as_ptr(), st.as_mut_ptr()) };
+        if s != 0 { fatal(s) }
+        unsafe { st.assume_init() }
+    }
+    /// The kernels the last repair call on this coder launched (folded, staged and generic launches
+    /// and stripes, the folded and staged launches' waves per workgroup and workgroups per stripe).
+    pub fn repair_launch_stats(&self) -> ffi::te_repair_launch_stats {
+        let mut st = std::mem::MaybeUninit::<ffi::te_repair_launch_stats>::zeroed();
+        let s = unsafe { ffi::te_clay_repair_launch_stats(self.raw.as_ptr(), st.as_mut_ptr()) };
+        if s != 0 { fatal(s) }
+        unsafe { st.assume_init() }
+    }
 }
 
 impl ErasureCoder for ClayCoder {

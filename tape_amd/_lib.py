@@ -93,6 +93,19 @@ class te_decode_launch_stats(C.Structure):
                 ("table_stripes", C.c_uint64), ("generic_stripes", C.c_uint64), ("jit_stripes", C.c_uint64)]
 
 
+class te_encode_launch_stats(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("dma_launches", "dma_level1_launches", "dma_level2_launches",
+                                          "stage_launches", "stage_masked_launches", "stage_g", "stage_wgs",
+                                          "generic_launches")] + \
+               [(f, C.c_uint64) for f in ("dma_stripes", "stage_stripes", "generic_stripes")]
+
+
+class te_repair_launch_stats(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("fold_launches", "stage_launches", "generic_launches", "fold_g", "fold_wgs",
+                                          "stage_g", "stage_wgs", "pad_")] + \
+               [(f, C.c_uint64) for f in ("fold_stripes", "stage_stripes", "generic_stripes")]
+
+
 def build(verbose: bool = False) -> str:
     """Compile libtapeec.so for gfx950 with hipcc (make -C tape_amd)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True,
@@ -126,6 +139,8 @@ def _load() -> C.CDLL:
         "te_clay_set_decode_store_cap": (i, [vp, u32]),
         "te_clay_decode_store_stats": (i, [vp, u32p, u32p, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]),
         "te_clay_decode_launch_stats": (i, [vp, C.POINTER(te_decode_launch_stats)]),
+        "te_clay_encode_launch_stats": (i, [vp, C.POINTER(te_encode_launch_stats)]),
+        "te_clay_repair_launch_stats": (i, [vp, C.POINTER(te_repair_launch_stats)]),
         "te_version": (C.c_char_p, []),
         "te_kernel_timing": (C.c_int, [C.c_int]),
         "te_kernel_time_ms": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),

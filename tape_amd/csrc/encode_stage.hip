@@ -635,16 +635,19 @@ bool encode_rows_supported(int n, int k, int d) { return n == 20 && d == k + 9 &
 
 // waves per workgroup: every column group of the stripe when they fit (kMaxG), or at most
 // a.groups_per_wg when the caller set it (small batches: more, shorter workgroups per stripe)
-static uint32_t stage_g(const EncArgs &a) {
+uint32_t encode_stage_g(const EncArgs &a) {
     uint32_t g = a.groups_per_stripe < (uint32_t)stage::kMaxG ? a.groups_per_stripe : (uint32_t)stage::kMaxG;
     if (a.groups_per_wg && a.groups_per_wg < g) g = a.groups_per_wg;
     return g;
 }
 
+uint32_t encode_stage_wgs(const EncArgs &a) {
+    const uint32_t g = encode_stage_g(a);
+    return (a.groups_per_stripe + g - 1) / g;
+}
+
 size_t encode_rows_scratch_bytes(const EncArgs &a) {
-    const uint32_t g = stage_g(a);
-    const uint32_t wgs = (a.groups_per_stripe + g - 1) / g;
-    return (size_t)a.njobs * wgs * stage::kScratchRows * g * 256u;
+    return (size_t)a.njobs * encode_stage_wgs(a) * stage::kScratchRows * encode_stage_g(a) * 256u;
 }
 
 template <int K, int G, bool MASKED>
@@ -659,9 +662,9 @@ hipError_t launch_stage_g(const EncArgs &a, uint64_t blocks, hipStream_t s) {
 template <int K, bool MASKED>
 hipError_t launch_stage(EncArgs a, hipStream_t s) {
     if (a.njobs == 0) return hipSuccess;
-    const uint32_t g = stage_g(a);
+    const uint32_t g = encode_stage_g(a);
+    a.wgs_per_stripe = encode_stage_wgs(a);
     a.groups_per_wg = g;
-    a.wgs_per_stripe = (a.groups_per_stripe + g - 1) / g;
     a.stripes_per_wg = 1;
     const uint64_t blocks = (uint64_t)a.njobs * a.wgs_per_stripe;
     if (blocks > 0x7fffffffull || !a.scratch) return hipErrorInvalidValue;

@@ -536,6 +536,9 @@ struct te_clay {
     // the decode_enqueue launches of the last decode / recover call (te_clay_decode_launch_stats):
     // zeroed when the call starts its device work, summed over its decode_enqueue passes
     te_decode_launch_stats dls{};
+    // the same for the encode_enqueue / repair_enqueue launches of the last encode / repair call
+    te_encode_launch_stats els{};
+    te_repair_launch_stats rls{};
 };
 
 // Drain and free everything a handle holds on its device (on that device).
@@ -759,6 +762,20 @@ int te_clay_decode_launch_stats(te_clay *c, te_decode_launch_stats *out) {
     if (!c || !out) return TE_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     *out = c->dls;
+    return TE_OK;
+}
+
+int te_clay_encode_launch_stats(te_clay *c, te_encode_launch_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->els;
+    return TE_OK;
+}
+
+int te_clay_repair_launch_stats(te_clay *c, te_repair_launch_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->rls;
     return TE_OK;
 }
 
@@ -1051,6 +1068,7 @@ int encode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, 
     };
     size_t gi = 0;
     std::vector<std::pair<bool, EncArgs>> level2;  // split launches' level-2 halves, enqueued last
+    te_encode_launch_stats &els = c->els;  // summed: the calling entry point zeroed it
     for (const Launch &L : launches) {
         const uint32_t cs = (uint32_t)L.key.cs, sc = cs / (uint32_t)h.alpha;
         const uint32_t wps = (sc + 3) / 4;   // words incl. a 2-column tail when sc % 4 == 2
@@ -1070,6 +1088,7 @@ int encode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, 
                 const uint32_t per = per_call ? 1u : g_enc_split_batch;
                 a.z0_first = 0; a.z0_count = per; a.z0_split = (7 + per - 1) / per; a.z0_limit = 7;
                 TE_HIP(launch_encode_dma(L.key.masked, a, s));
+                els.dma_level1_launches++;
                 a.z0_limit = 0;
                 a.z0_first = 7; a.z0_count = 3; a.z0_split = 1;   // level 2 reads their parity back:
                 a.queue = queues + qi++;
@@ -1077,6 +1096,8 @@ int encode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, 
             } else {
                 TE_HIP(launch_encode_dma(L.key.masked, a, s));
             }
+            els.dma_launches++;
+            els.dma_stripes += L.count;
         } else if (fast_path(L)) {
             (void)full;
             EncArgs a{};
@@ -1091,12 +1112,23 @@ int encode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, 
             a.n = (uint32_t)n;
             a.scratch = scratch;
             TE_HIP(launch_encode_rows(h.k, L.key.masked, a, s));
+            els.stage_launches++;
+            els.stage_masked_launches += L.key.masked ? 1u : 0u;
+            els.stage_stripes += L.count;
+            els.stage_g = encode_stage_g(a);
+            els.stage_wgs = encode_stage_wgs(a);
         } else {
             TE_HIP(launch_gpe(gpe_args(gi, L, 0, wps), (uint32_t)pat.nerased, s));
+            els.generic_launches++;
+            els.generic_stripes += L.count;
         }
         gi++;
     }
-    for (const auto &l2 : level2) TE_HIP(launch_encode_dma(l2.first, l2.second, s));
+    for (const auto &l2 : level2) {
+        TE_HIP(launch_encode_dma(l2.first, l2.second, s));
+        els.dma_launches++;
+        els.dma_level2_launches++;
+    }
     kt.stop();
     return A.mark_done(s);
 }
@@ -1907,13 +1939,24 @@ int repair_enqueue(te_clay *c, const uint8_t *d_helpers, const RepItem *items, s
         a.groups_per_stripe = (wps + kGpeWords - 1) / kGpeWords;
         a.cs = (uint32_t)cs; a.sc = sc; a.q = h.q; a.t = h.t; a.alpha = h.alpha;
         for (int i = 0; i < 16; i++) a.qpow[i] = h.qpow[i];
+        te_repair_launch_stats &rls = c->rls;  // summed: the calling entry point zeroed it
         if (o.fold >= 0) {
             TE_HIP(launch_repair_fold(a, s));
+            rls.fold_launches++;
+            rls.fold_stripes += o.njobs;
+            rls.fold_g = repair_fold_g(wps);
+            rls.fold_wgs = repair_wgs(wps, rls.fold_g);
         } else if (staged && sc >= 8) {  // staged kernel: coalesced loads, whole-row stores
             a.progs = A.at<RepProg>(prog_off);
             TE_HIP(launch_repair_stage(a, s));
+            rls.stage_launches++;
+            rls.stage_stripes += o.njobs;
+            rls.stage_g = repair_stage_g(wps);
+            rls.stage_wgs = repair_wgs(wps, rls.stage_g);
         } else {
             TE_HIP(launch_repair(a, max_er, s));
+            rls.generic_launches++;
+            rls.generic_stripes += o.njobs;
         }
     }
     kt.stop();
@@ -2027,6 +2070,7 @@ static int encode_host_impl(te_clay *c, const te_slicer_cfg *cfg, const uint8_t 
         out_bytes[i] = (uint64_t)n * g.slice_len;
     }
     std::lock_guard<std::mutex> lk(c->mu);
+    c->els = te_encode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     // three slot streams: the handle's two pipe streams and its own stream -- the same three the
@@ -2701,6 +2745,7 @@ static int encode_commit_host_impl(te_clay *c, const te_slicer_cfg *cfg, const u
     const uint64_t commit_cap = L.max_group_obj * (B.leaf_b + TE_HASH_SIZE + B.proof_b);
 
     std::lock_guard<std::mutex> lk(c->mu);
+    c->els = te_encode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     // three streams: two slot streams and the hashing stream (a fifth stream beside the caller's
@@ -2889,6 +2934,7 @@ int te_encode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     if (!c || !cfg || (!objs && nobj)) return TE_ERR_INVALID_ARG;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
     std::lock_guard<std::mutex> lk(c->mu);
+    c->els = te_encode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     return encode_enqueue(c, cfg, d_data, objs, nobj, d_out, (hipStream_t)stream, false);
@@ -2986,6 +3032,10 @@ int te_stream_submit(te_stream_writer *w, const uint8_t *h_data, const te_object
     B.co = CommitOut{h_leaf_hashes, h_roots, h_proofs, w->height};
     // every per-object check happens here, before the window touches the device's open group
     int rc = commit_prepare(c, B);
+    if (!rc) {  // the window's group_add passes below sum into it
+        std::lock_guard<std::mutex> lk(c->mu);
+        c->els = te_encode_launch_stats{};
+    }
     auto pend_t = [&] {
         if (d.pend.empty() || d.pend.back() != t) d.pend.push_back(t);
         T.pending = true;
@@ -3230,6 +3280,7 @@ int te_repair_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair
         items[i] = RepItem{objs[i].plan, objs[i].helper_off, objs[i].out_off, objs[i].metadata};
     }
     std::lock_guard<std::mutex> lk(c->mu);
+    c->rls = te_repair_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     return repair_enqueue(c, d_helpers, items.data(), items.size(), d_out, (hipStream_t)stream);
@@ -3251,6 +3302,7 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
     if (!part) {
         std::lock_guard<std::mutex> lk(c->mu);
         c->dls = te_decode_launch_stats{};
+        c->els = te_encode_launch_stats{};  // the keep-filter re-encode of the parity-lost stripes
     }
     const ClayHost &h = c->h;
     const uint32_t n = (uint32_t)h.n;
@@ -3481,6 +3533,7 @@ int te_slicer_encode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *data, 
     const size_t total = (size_t)c->h.n * g.slice_len;
     if (cap < total) return TE_ERR_BUFFER_TOO_SMALL;
     std::lock_guard<std::mutex> lk(c->mu);
+    c->els = te_encode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     int r = ensure_stream(c);
@@ -3507,6 +3560,7 @@ int te_clay_encode(te_clay *c, const uint8_t *data, size_t len, uint8_t *chunks,
     if (chunk_size) *chunk_size = cs;
     if (cap < total) return TE_ERR_BUFFER_TOO_SMALL;
     std::lock_guard<std::mutex> lk(c->mu);
+    c->els = te_encode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     int r = ensure_stream(c);
@@ -3837,6 +3891,7 @@ int te_slicer_repair(te_clay *c, const te_repair_plan *p, const uint8_t *const *
         total += (need[sl] + 15) & ~15ull;
     }
     std::lock_guard<std::mutex> lk(c->mu);
+    c->rls = te_repair_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     int r = ensure_stream(c);

@@ -339,6 +339,10 @@ __host__ __device__ inline uint64_t verify_blocks(uint64_t len) { return (len + 
 hipError_t launch_verify(const VerifyArgs &a, const VerifyItem *h_items, hipStream_t s);
 
 hipError_t launch_encode_rows(int k, bool masked, const EncArgs &a, hipStream_t s);
+// the geometry launch_encode_rows gives `a` (a.groups_per_stripe, a.groups_per_wg set): waves per
+// workgroup, workgroups per stripe
+uint32_t encode_stage_g(const EncArgs &a);
+uint32_t encode_stage_wgs(const EncArgs &a);
 // encode_dma.hip: Clay(20,7,16), 1,280 < sub-chunk <= 1,440 bytes (the 1 MB stripes), no scratch
 bool encode_dma_supported(int n, int k, uint32_t sc);
 hipError_t launch_encode_dma(bool masked, const EncArgs &a, hipStream_t s);
@@ -438,6 +442,11 @@ int repair_fold_column(uint32_t q, uint32_t t, uint32_t k, uint32_t beta, uint32
                        uint64_t erased_mask, uint64_t aloof_mask);
 hipError_t launch_repair_fold(RepArgs a, hipStream_t s);
 bool repair_stage_supported(uint32_t q, uint32_t beta, uint32_t sc, uint32_t nerased, uint32_t nknown, uint64_t aloof_mask);
+// waves per workgroup of launch_repair_fold / launch_repair_stage for a.words_per_stripe words; they
+// start ceil(groups / g) workgroups per stripe, groups = ceil(words_per_stripe / 64)
+uint32_t repair_fold_g(uint32_t words_per_stripe);
+uint32_t repair_stage_g(uint32_t words_per_stripe);
+inline uint32_t repair_wgs(uint32_t words_per_stripe, uint32_t g) { return ((words_per_stripe + 63) / 64 + g - 1) / g; }
 bool encode_rows_supported(int n, int k, int d);
 size_t encode_rows_scratch_bytes(const EncArgs &a);  // a.njobs, a.groups_per_stripe set
 

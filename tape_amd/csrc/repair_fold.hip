@@ -360,12 +360,16 @@ static hipError_t fold_dispatch(uint32_t g, const RepArgs &a, uint64_t blocks, h
     return launch_fold_g<G>(a, blocks, s);
 }
 
+uint32_t repair_fold_g(uint32_t words_per_stripe) {
+    const uint32_t groups = (words_per_stripe + 63) / 64;
+    return groups < (uint32_t)rfold::kMaxG ? groups : (uint32_t)rfold::kMaxG;
+}
+
 hipError_t launch_repair_fold(RepArgs a, hipStream_t s) {
     if (a.njobs == 0) return hipSuccess;
     if (a.sc < 8) return hipErrorInvalidValue;
-    const uint32_t groups = (a.words_per_stripe + 63) / 64;
-    const uint32_t g = groups < (uint32_t)rfold::kMaxG ? groups : (uint32_t)rfold::kMaxG;
-    a.wgs_per_stripe = (groups + g - 1) / g;
+    const uint32_t g = repair_fold_g(a.words_per_stripe);
+    a.wgs_per_stripe = repair_wgs(a.words_per_stripe, g);
     const uint64_t blocks = (uint64_t)a.njobs * a.wgs_per_stripe;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     // waves per workgroup (g <= kMaxG; small sub-chunks use fewer): only 1..kMaxG are built

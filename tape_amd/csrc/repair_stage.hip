@@ -211,11 +211,15 @@ static hipError_t rep_stage_dispatch(uint32_t g, const RepArgs &a, uint64_t bloc
     return launch_rep_stage_g<G>(a, blocks, s);
 }
 
+uint32_t repair_stage_g(uint32_t words_per_stripe) {
+    const uint32_t groups = (words_per_stripe + 63) / 64;
+    return groups < (uint32_t)rstage::kMaxG ? groups : (uint32_t)rstage::kMaxG;
+}
+
 hipError_t launch_repair_stage(RepArgs a, hipStream_t s) {
     if (a.njobs == 0) return hipSuccess;
-    const uint32_t groups = (a.words_per_stripe + 63) / 64;
-    const uint32_t g = groups < (uint32_t)rstage::kMaxG ? groups : (uint32_t)rstage::kMaxG;
-    a.wgs_per_stripe = (groups + g - 1) / g;
+    const uint32_t g = repair_stage_g(a.words_per_stripe);
+    a.wgs_per_stripe = repair_wgs(a.words_per_stripe, g);
     const uint64_t blocks = (uint64_t)a.njobs * a.wgs_per_stripe;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
     return rep_stage_dispatch<rstage::kMaxG>(g, a, blocks, s);  // only 1..kMaxG waves are built

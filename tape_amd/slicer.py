@@ -308,6 +308,23 @@ class ClayCoder:
         d["class_launches"] = {i: int(v) for i, v in enumerate(st.class_launches) if v}
         return d
 
+    def encode_launch_stats(self) -> dict:
+        """te_clay_encode_launch_stats: the kernels the handle's last encode call launched -- launches
+        and stripes of the LDS-DMA, staged and generic kernels, the split level-1 / level-2 LDS-DMA
+        launches, the masked staged launches, and the last staged launch's waves per workgroup and
+        workgroups per stripe."""
+        st = _lib.te_encode_launch_stats()
+        _check(lib.te_clay_encode_launch_stats(self.handle, C.byref(st)), "encode")
+        return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+    def repair_launch_stats(self) -> dict:
+        """te_clay_repair_launch_stats: the kernels the handle's last repair call launched -- launches
+        and stripes of the folded, staged and generic kernels, and the last folded and staged
+        launch's waves per workgroup and workgroups per stripe."""
+        st = _lib.te_repair_launch_stats()
+        _check(lib.te_clay_repair_launch_stats(self.handle, C.byref(st)), "repair")
+        return {f: int(getattr(st, f)) for f, _ in st._fields_ if f != "pad_"}
+
     def decode_jit_status(self, timeout_ms: int = 0) -> tuple:
         """(ready, compiling, failed) per-pattern kernels, after waiting up to timeout_ms."""
         v = [C.c_uint32(0) for _ in range(3)]

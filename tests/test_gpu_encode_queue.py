@@ -40,13 +40,16 @@ def _grid(monkeypatch, g):
 
 
 def _encode_check(oracle, o716, sizes, gap=0, repeat=1):
-    """encode_batch of objects (seed i, sizes[i]) laid gap bytes apart; every slice against the oracle."""
+    """encode_batch of objects (seed i, sizes[i]) laid gap bytes apart; every slice against the oracle,
+    and every stripe of the call on the LDS-DMA kernel (te_clay_encode_launch_stats): one unsplit
+    launch per (slice length, data end dword aligned or not).  Returns those launch groups."""
     from tape_amd import batch
     s = T.Slicer.clay_default()
     offs, outs, cur, ocur = [], [], 0, 0
     for ln in sizes:
         offs.append(cur)
         cur += ln + gap
+        cur += cur & 1  # even addresses only: a stripe at an odd one runs the generic kernel
         outs.append(ocur)
         ocur += N * s.geometry(ln).slice_len
     host = np.zeros(cur, np.uint8)
@@ -54,6 +57,15 @@ def _encode_check(oracle, o716, sizes, gap=0, repeat=1):
         host[offs[i]:offs[i] + ln] = _data(oracle, i, ln)
     d_in = torch.from_numpy(host).to("cuda:0")
     d_out = torch.empty(ocur, dtype=torch.uint8, device="cuda:0")
+    assert d_in.data_ptr() % 4 == 0
+    groups, stripes = set(), 0
+    for i, ln in enumerate(sizes):
+        g = s.geometry(ln)
+        for st in range(g.num_stripes):
+            a, src_len = offs[i] + st * g.stripe_size, min(g.stripe_size, ln - st * g.stripe_size)
+            assert a % 2 == 0
+            groups.add((g.slice_len, (a % 4 + src_len) % 4 != 0))
+            stripes += 1
     for _ in range(repeat):
         d_out.fill_(0xA5)
         batch.encode_batch(s, d_in, [(offs[i], sizes[i], outs[i], 0) for i in range(len(sizes))], d_out)
@@ -62,6 +74,11 @@ def _encode_check(oracle, o716, sizes, gap=0, repeat=1):
         for i, ln in enumerate(sizes):
             exp = _expect(oracle, o716, i, ln)
             assert np.array_equal(out[outs[i]:outs[i] + exp.size].reshape(N, -1), exp), (i, ln)
+        st = s.coder.encode_launch_stats()
+        assert st["dma_stripes"] == stripes and st["dma_launches"] == len(groups), st
+        assert st["dma_level1_launches"] == st["dma_level2_launches"] == 0, st
+        assert st["stage_launches"] == st["generic_launches"] == st["stage_stripes"] == st["generic_stripes"] == 0, st
+    return groups
 
 
 @pytest.mark.parametrize("sizes", [
@@ -87,9 +104,14 @@ def test_full_and_short_stripes_alternate(oracle, o716, monkeypatch, g):
 @pytest.mark.parametrize("g", [1, 3])
 def test_masked_and_unmasked_launches(oracle, o716, monkeypatch, g):
     """Dword-aligned and unaligned data ends get a launch (and a queue counter) each in one call.
-    The 2-byte gap leaves later objects 2-aligned only (odd offsets do not run the LDS-DMA kernel)."""
+    The 2-byte gap (3 after an odd length) leaves later objects 2-aligned only (odd offsets do not run
+    the LDS-DMA kernel)."""
     _grid(monkeypatch, g)
-    _encode_check(oracle, o716, [4 * MiB, MiB, 1_000_001, 2_000_003, 1_999_998], gap=2)
+    groups = _encode_check(oracle, o716, [4 * MiB, MiB, 1_000_001, 2_000_003, 1_999_998], gap=2)
+    # the two-stripe objects share a slice length and have stripes ending dword aligned and not: a
+    # launch of each kind
+    two = T.Slicer.clay_default().geometry(MiB).slice_len
+    assert {m for sl, m in groups if sl == two} == {False, True}
 
 
 def test_last_task_without_successor(oracle, o716, monkeypatch):

@@ -36,6 +36,9 @@ def test_repair_one_peer_down_rotated(encoded_4mib):
         down = (lost + 10) % N
         helpers = [(i, sl[i]) for i in range(N) if i not in (lost, down)]
         assert s.repair_full(lost, helpers) == sl[lost], (lost, down)
+        st = s.coder.repair_launch_stats()
+        assert (st["fold_launches"], st["fold_stripes"]) == (1, s.geometry(4 * MiB).num_stripes), st
+        assert st["stage_launches"] == st["generic_launches"] == 0, st
 
 
 @pytest.mark.parametrize("lost", [0, 4, 9, 10, 16, 19])
@@ -52,11 +55,13 @@ def test_repair_every_single_down_identity(oracle, lost):
 
 
 def test_repair_two_down_identity(oracle):
-    """Two of the other column down: no folded set, the table-driven kernel; and a column-mate down
-    is minimum_to_repair's error (RepairError::Clay)."""
+    """Two of the other column down: the table-driven kernel, unless the first 7 available nodes are
+    still a folded set (both down nodes past the first 7, or one of them and one of the last 2); and
+    a column-mate down is minimum_to_repair's error (RepairError::Clay)."""
     s = T.Slicer.new(T.ClayCoder(20, 7, 16))
     data = oracle.splitmix64_bytes(77, 3 * MiB).tobytes()
     sl = s.encode(data)
+    ns = s.geometry(len(data)).num_stripes
     rnd = random.Random(5)
     for lost in (2, 13):
         other = 10 if lost < 10 else 0
@@ -64,6 +69,13 @@ def test_repair_two_down_identity(oracle):
             downs = rnd.sample(range(other, other + 10), 2)
             helpers = [(i, sl[i]) for i in range(N) if i != lost and i not in downs]
             assert s.repair_full(lost, helpers) == sl[lost], (lost, downs)
+            # the first 7 available of the other column are a folded set only if at most one of its
+            # first 7 is down and the other down node is not the eighth
+            lo, hi = sorted(d % 10 for d in downs)
+            folded = lo >= 7 or (lo < 7 and hi >= 8)
+            st = s.coder.repair_launch_stats()
+            assert st["generic_launches"] == 0 and st["fold_stripes" if folded else "stage_stripes"] == ns, (downs, st)
+            assert st["stage_stripes" if folded else "fold_stripes"] == 0, (downs, st)
         mate = (lost // 10) * 10 + (lost % 10 + 1) % 10
         with pytest.raises(T.RepairError) as e:
             s.repair_full(lost, [(i, sl[i]) for i in range(N) if i not in (lost, mate)])
@@ -87,6 +99,9 @@ def test_clay_repair_sets_match_oracle(oracle):
             assert plan == o.minimum_to_repair(lost, avail), (lost, p)
             helpers = {h: b"".join(ch[h][z * sc:(z + 1) * sc] for z in pl) for h, pl in plan}
             assert c.repair(lost, helpers, cs) == ch[lost], (lost, p)
+            st = c.repair_launch_stats()  # one node of the other column down: a folded set
+            assert (st["fold_launches"], st["fold_stripes"]) == (1, 1), (lost, p, st)
+            assert st["stage_launches"] == st["generic_launches"] == 0, (lost, p, st)
 
 
 def test_repair_batch_peer_down(oracle):
@@ -123,6 +138,9 @@ def test_repair_batch_peer_down(oracle):
     d_rep = torch.zeros(nobj * g.slice_len, dtype=torch.uint8, device=dev)
     batch.repair_batch(s.coder, d_help, objs, d_rep)
     torch.cuda.synchronize()
+    st = s.coder.repair_launch_stats()  # one chunk size, every stripe a folded set: one launch
+    assert (st["fold_launches"], st["fold_stripes"]) == (1, nobj * g.num_stripes), st
+    assert st["stage_launches"] == st["generic_launches"] == 0, st
     rep = d_rep.cpu().numpy()
     for i in range(nobj):
         lost = i % N

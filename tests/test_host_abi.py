@@ -194,6 +194,26 @@ def test_decode_launch_stats_before_any_call():
     assert _lib.lib.te_clay_decode_launch_stats(c.handle, None) == _lib.TE_ERR_INVALID_ARG
 
 
+def test_encode_repair_launch_stats_before_any_call():
+    """te_clay_encode_launch_stats and te_clay_repair_launch_stats are host bookkeeping like the decode
+    stats: all zero on a fresh handle, no device needed, null arguments refused; the ctypes mirrors
+    have the C structs' sizes (8 32-bit and 3 64-bit fields each, no padding)."""
+    for name, method in (("encode", "encode_launch_stats"), ("repair", "repair_launch_stats")):
+        struct = getattr(_lib, "te_%s_launch_stats" % name)
+        fn = getattr(_lib.lib, "te_clay_%s_launch_stats" % name)
+        assert C.sizeof(struct) == 8 * 4 + 3 * 8
+        c = T.ClayCoder(20, 7, 16)
+        st = struct()
+        C.memset(C.byref(st), 0xFF, C.sizeof(st))
+        assert fn(c.handle, C.byref(st)) == 0
+        assert bytes(st) == bytes(C.sizeof(st))
+        d = getattr(c, method)()
+        assert d and all(v == 0 for v in d.values())
+        assert set(d) == {f for f, _ in struct._fields_} - {"pad_"}
+        assert fn(None, C.byref(st)) == _lib.TE_ERR_INVALID_ARG
+        assert fn(c.handle, None) == _lib.TE_ERR_INVALID_ARG
+
+
 def test_recover_needs_device():
     import ctypes as C
     from tape_amd import _lib
