@@ -595,6 +595,38 @@ int te_outer_decode_device(uint32_t k, uint32_t n, const uint8_t *const *d_chunk
  * without waiting. */
 int te_outer_decode_device_batch(uint32_t k, uint32_t n, const uint8_t *const *d_chunks, uint32_t segments,
                                  uint64_t chunk_bytes, uint8_t *d_out, uint64_t seg_out, void *hip_stream);
+/* Which kernels the calling thread's last te_outer_* call launched (diagnostics; host bookkeeping
+ * only, no effect on results).  The te_outer_* API has no handle, so the stats are per thread: one
+ * te_outer_encode / te_outer_encode_device / te_outer_decode / te_outer_decode_device /
+ * te_outer_decode_device_batch call, summed over its launches (a batch decode launches once per
+ * erasure pattern and 256 shard pointers).  Filled by the launchers where the kernel instance is
+ * picked.  Zeroed when such a call has passed its argument checks and starts its device work (an
+ * encode of te_outer_encode counts as that one call); all zero before the first one.  The
+ * geometry fields are those of the call's last such launch. */
+typedef struct te_outer_launch_stats {
+    uint32_t matrix_launches;    /* rs16_matrix_kernel: image <= 80 KiB, k <= 32, rows <= 64 */
+    uint32_t matrix_ptr_launches; /* of those, shards by pointer argument (the decode) */
+    uint32_t transform_launches; /* rs16_encode_kernel: the FFT encode, work vector in LDS */
+    uint32_t low_reg_launches;   /* rs16_encode_low_kernel: low rate, k <= 32, work vector in VGPRs */
+    uint32_t decode_launches;    /* rs16_decode_kernel: per-coefficient nibble tables */
+    uint32_t matrix_g, matrix_kb; /* 4-row groups (1..16) and input slots (16 / 32) of the instance */
+    uint32_t matrix_tail_bytes;  /* entry bytes of an odd G's last group: 2 / 4 / 8 (0: even G, or
+                                    the last row on the VALU) */
+    uint32_t matrix_tailv;       /* 1: the last row of rows = 8 h + 1 on the VALU */
+    uint32_t matrix_grid, matrix_tiles; /* workgroups started, (segment, 512-thread column tile)
+                                    pairs they loop over */
+    uint32_t transform_high;     /* 1 high rate, 0 low rate */
+    uint32_t transform_threads;  /* workgroup size picked for the LDS the shape needs */
+    uint32_t transform_c;        /* transform size */
+    uint32_t transform_lds;      /* dynamic LDS bytes of the launch */
+    uint32_t low_reg_c;          /* transform size of the instance: 1, 2, 4, 8, 16, 32 */
+    uint32_t decode_kb;          /* input slots of the instance: 4..32 (k <= 32), 0: any k */
+    uint32_t decode_lds;         /* 1: tables staged in LDS (<= 48 KiB), 0: read from L2 */
+    uint32_t lut_misses;         /* matrix images / decoding tables built and uploaded by the call */
+    uint32_t lut_evictions;      /* least recently used tables it freed to stay within 64 */
+    uint64_t matrix_segments, transform_segments, low_reg_segments, decode_segments;
+} te_outer_launch_stats;
+int te_outer_last_launch_stats(te_outer_launch_stats *out);
 
 #ifdef __cplusplus
 }

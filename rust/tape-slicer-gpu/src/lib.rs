@@ -325,6 +325,13 @@ impl OuterCoder {
         })?;
         Ok(out)
     }
+    /// te_outer_last_launch_stats: the kernels this thread's last encode or decode launched.
+    pub fn launch_stats() -> ffi::te_outer_launch_stats {
+        let mut st = std::mem::MaybeUninit::<ffi::te_outer_launch_stats>::zeroed();
+        let s = unsafe { ffi::te_outer_last_launch_stats(st.as_mut_ptr()) };
+        if s != 0 { fatal(s) }
+        unsafe { st.assume_init() }
+    }
 }
 
 /// Page-locked host memory (te_host_alloc): the host <-> device copies of a window run from and

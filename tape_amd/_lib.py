@@ -106,6 +106,16 @@ class te_repair_launch_stats(C.Structure):
                [(f, C.c_uint64) for f in ("fold_stripes", "stage_stripes", "generic_stripes")]
 
 
+class te_outer_launch_stats(C.Structure):
+    _fields_ = [(f, C.c_uint32) for f in ("matrix_launches", "matrix_ptr_launches", "transform_launches",
+                                          "low_reg_launches", "decode_launches", "matrix_g", "matrix_kb",
+                                          "matrix_tail_bytes", "matrix_tailv", "matrix_grid", "matrix_tiles",
+                                          "transform_high", "transform_threads", "transform_c", "transform_lds",
+                                          "low_reg_c", "decode_kb", "decode_lds", "lut_misses", "lut_evictions")] + \
+               [(f, C.c_uint64) for f in ("matrix_segments", "transform_segments", "low_reg_segments",
+                                          "decode_segments")]
+
+
 def build(verbose: bool = False) -> str:
     """Compile libtapeec.so for gfx950 with hipcc (make -C tape_amd)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True,
@@ -224,6 +234,7 @@ def _load() -> C.CDLL:
         "te_outer_encode_device": (i, [u32, u32, vp, u64, u32, u64, vp, u64, vp]),
         "te_outer_decode_device": (i, [u32, u32, pp, u64, vp, vp]),
         "te_outer_decode_device_batch": (i, [u32, u32, pp, u32, u64, vp, u64, vp]),
+        "te_outer_last_launch_stats": (i, [C.POINTER(te_outer_launch_stats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

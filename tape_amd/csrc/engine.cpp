@@ -4446,6 +4446,16 @@ size_t te_outer_chunk_bytes(uint32_t k, size_t len) {  // outer.rs:74-80
 namespace {
 int outer_encode_matrix(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint32_t segments,
                         uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, hipStream_t s);
+// te_outer_launch_stats: the outermost te_outer_* call on this thread zeroes the stats once its
+// arguments are checked (te_outer_encode calls te_outer_encode_device); the launchers
+// (rs16.hip) and outer_lut add to them
+thread_local int g_outer_depth = 0;
+struct OuterCall {
+    OuterCall() { if (g_outer_depth++ == 0) rs16_launch_stats() = te_outer_launch_stats{}; }
+    ~OuterCall() { g_outer_depth--; }
+    OuterCall(const OuterCall &) = delete;
+    OuterCall &operator=(const OuterCall &) = delete;
+};
 }
 extern "C" {
 
@@ -4455,6 +4465,7 @@ int te_outer_encode_device(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t
         return TE_ERR_INVALID_ARG;
     if (rs16::use_high_rate(k, m) < 0) return TE_ERR_UNSUPPORTED;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    const OuterCall call;
     // the encode as a matrix product (rs16_matrix_kernel) when its lookup image fits the LDS budget:
     // OuterCoder(17, 50) 17 x 33; the transforms below otherwise
     if (rs16_mat_supported(k, m) && !tec_knob("TEC_RS16_NO_MATRIX"))
@@ -4507,6 +4518,7 @@ int te_outer_encode(uint32_t k, uint32_t n, const uint8_t *data, size_t len, uin
     if (m == 0) return TE_OK;
     if (rs16::use_high_rate(k, m) < 0) return TE_ERR_UNSUPPORTED;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    const OuterCall call;
     uint8_t *d = nullptr;
     TE_HIP(hipMalloc((void **)&d, (size_t)n * cb));
     int r = hip_status(hipMemcpy(d, out, (size_t)k * cb, hipMemcpyHostToDevice));
@@ -4548,6 +4560,7 @@ int outer_lut(uint32_t k, uint32_t m, const std::vector<uint32_t> &recv, const s
         out = &it->second;
         return TE_OK;
     }
+    rs16_launch_stats().lut_misses++;
     const uint32_t nm = (uint32_t)miss.size();
     const bool enc = nm == 1 && miss[0] == 0xfffffffeu;  // the encode matrix (outer_enc_lut)
     const uint32_t rows = enc ? m : nm;
@@ -4583,6 +4596,7 @@ int outer_lut(uint32_t k, uint32_t m, const std::vector<uint32_t> &recv, const s
         lru->second.readers.destroy();
         (void)hipFree(lru->second.d);
         g_outer_luts.erase(lru);
+        rs16_launch_stats().lut_evictions++;
     }
     OuterLut L;
     TE_HIP(hipMalloc((void **)&L.d, lut.size() * sizeof(uint16_t)));
@@ -4670,6 +4684,7 @@ int te_outer_decode(uint32_t k, uint32_t n, const uint8_t *const *chunks, size_t
     if (chunk_bytes == 0 || chunk_bytes % 64) return TE_ERR_INVALID_LAYOUT;  // the decoder's shard-size check
     if (rs16::use_high_rate(k, m) < 0 || k > kRs16MaxK) return TE_ERR_UNSUPPORTED;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    const OuterCall call;
     std::vector<uint32_t> recv(have.begin(), have.begin() + k);  // any k shards determine the originals
     const uint32_t nm = (uint32_t)miss.size();
     int dev = 0;
@@ -4734,6 +4749,7 @@ int outer_decode_segs(uint32_t k, uint32_t n, const uint8_t *const *d_chunks, ui
         groups[key].push_back(g);
     }
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    const OuterCall call;
     int r = TE_OK;
     for (uint32_t g = 0; g < segments && r == TE_OK; g++)
         for (uint32_t i = 0; i < k && r == TE_OK; i++)
@@ -4767,6 +4783,12 @@ int outer_decode_segs(uint32_t k, uint32_t n, const uint8_t *const *d_chunks, ui
 }  // namespace
 
 extern "C" {
+
+int te_outer_last_launch_stats(te_outer_launch_stats *out) {
+    if (!out) return TE_ERR_INVALID_ARG;
+    *out = rs16_launch_stats();
+    return TE_OK;
+}
 
 int te_outer_decode_device(uint32_t k, uint32_t n, const uint8_t *const *d_chunks, uint64_t chunk_bytes,
                            uint8_t *d_out, void *stream) {

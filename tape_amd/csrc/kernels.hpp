@@ -6,6 +6,8 @@
 #include "gf.hpp"
 #include "dec_fixed.hpp"
 
+struct te_outer_launch_stats;  // include/tape_ec.h
+
 namespace tec {
 
 // Measurement knobs (kernel variants, JIT geometry, forced windows) are read from the environment
@@ -429,6 +431,9 @@ inline size_t rs16_mat_image_bytes(uint32_t k, uint32_t rows) {  // + the tail r
 inline bool rs16_mat_supported(uint32_t k, uint32_t rows) {
     return k >= 1 && k <= 32 && rows >= 1 && (rows + 3) / 4 <= kRs16MatMaxG && rs16_mat_bytes(k, rows) <= kRs16MatLds;
 }
+// the calling thread's te_outer_launch_stats (tape_ec.h): the three launchers below add each launch
+// they start, with the instance they picked; the te_outer_* entry points zero it (engine.cpp)
+te_outer_launch_stats &rs16_launch_stats();
 hipError_t launch_rs16_matrix(const Rs16MatArgs &a, hipStream_t s);
 hipError_t launch_rs16_encode(const Rs16EncArgs &a, uint32_t segments, hipStream_t s);
 hipError_t launch_rs16_decode(const Rs16DecArgs &a, uint32_t segments, hipStream_t s);

@@ -12,8 +12,15 @@
 // A first kernel: correct for every shard count the crate supports within the LDS budget.
 #include <algorithm>
 #include "kernels.hpp"
+#include "../../include/tape_ec.h"
 
 namespace tec {
+
+te_outer_launch_stats &rs16_launch_stats() {
+    static thread_local te_outer_launch_stats st{};
+    return st;
+}
+
 namespace rs16k {
 
 constexpr uint32_t kRs16DecLds = 48 * 1024;  // decoding tables staged in LDS up to this size
@@ -547,7 +554,19 @@ hipError_t launch_mat_gkt(Rs16MatArgs a, uint32_t grid, size_t lds, hipStream_t 
     if (const hipError_t e = ensure_dyn_lds(fn, lds); e != hipSuccess) return e;
     if (a.ptrs) hipLaunchKernelGGL((rs16_matrix_kernel<G, KB, true, TV, TB>), dim3(grid), dim3(kMatBT), lds, s, a);
     else hipLaunchKernelGGL((rs16_matrix_kernel<G, KB, false, TV, TB>), dim3(grid), dim3(kMatBT), lds, s, a);
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {  // the instance that ran: te_outer_launch_stats
+        te_outer_launch_stats &st = rs16_launch_stats();
+        st.matrix_launches++;
+        st.matrix_ptr_launches += a.ptrs ? 1u : 0u;
+        st.matrix_segments += a.segments;
+        st.matrix_g = G;
+        st.matrix_kb = KB;
+        st.matrix_tail_bytes = (G % 2 && !TV) ? TB : 0;
+        st.matrix_tailv = TV;
+        st.matrix_grid = grid;
+    }
+    return e;
 }
 template <int G, int KB>
 hipError_t launch_mat_gk(const Rs16MatArgs &a, uint32_t grid, size_t lds, hipStream_t s) {
@@ -663,7 +682,15 @@ hipError_t launch_dec_kb(const Rs16DecArgs &a, dim3 grid, dim3 block, size_t lds
         if (lds) hipLaunchKernelGGL((rs16_decode_kernel<0, true>), grid, block, lds, s, a);
         else hipLaunchKernelGGL((rs16_decode_kernel<0, false>), grid, block, 0, s, a);
     }
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {  // the instance that ran: te_outer_launch_stats
+        te_outer_launch_stats &st = rs16_launch_stats();
+        st.decode_launches++;
+        st.decode_segments += grid.y;
+        st.decode_kb = KB <= 32 ? KB : 0;
+        st.decode_lds = lds ? 1u : 0u;
+    }
+    return e;
 }
 
 }  // namespace rs16k
@@ -709,15 +736,23 @@ hipError_t launch_rs16_encode(const Rs16EncArgs &a, uint32_t segments, hipStream
         }
         const hipError_t e = ensure_dyn_lds(fn, lds);
         if (e != hipSuccess) return e;
+        uint32_t inst = 0;  // the instance launched: te_outer_launch_stats
         switch (a.c) {
-        case 1: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<1>, grid, dim3(256), lds, s, a); break;
-        case 2: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<2>, grid, dim3(256), lds, s, a); break;
-        case 4: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<4>, grid, dim3(256), lds, s, a); break;
-        case 8: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<8>, grid, dim3(256), lds, s, a); break;
-        case 16: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<16>, grid, dim3(256), lds, s, a); break;
-        default: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<32>, grid, dim3(256), lds, s, a); break;
+        case 1: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<1>, grid, dim3(256), lds, s, a); inst = 1; break;
+        case 2: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<2>, grid, dim3(256), lds, s, a); inst = 2; break;
+        case 4: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<4>, grid, dim3(256), lds, s, a); inst = 4; break;
+        case 8: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<8>, grid, dim3(256), lds, s, a); inst = 8; break;
+        case 16: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<16>, grid, dim3(256), lds, s, a); inst = 16; break;
+        default: hipLaunchKernelGGL(rs16k::rs16_encode_low_kernel<32>, grid, dim3(256), lds, s, a); inst = 32; break;
         }
-        return hipGetLastError();
+        const hipError_t le = hipGetLastError();
+        if (le == hipSuccess) {
+            te_outer_launch_stats &st = rs16_launch_stats();
+            st.low_reg_launches++;
+            st.low_reg_segments += segments;
+            st.low_reg_c = inst;
+        }
+        return le;
     }
 #endif
     size_t lds = 0;
@@ -726,7 +761,17 @@ hipError_t launch_rs16_encode(const Rs16EncArgs &a, uint32_t segments, hipStream
     const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void *>(rs16k::rs16_encode_kernel), lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(rs16k::rs16_encode_kernel, dim3((uint32_t)((a.elems + t - 1) / t), segments), dim3(t), lds, s, a);
-    return hipGetLastError();
+    const hipError_t le = hipGetLastError();
+    if (le == hipSuccess) {  // what rs16_enc_threads picked: te_outer_launch_stats
+        te_outer_launch_stats &st = rs16_launch_stats();
+        st.transform_launches++;
+        st.transform_segments += segments;
+        st.transform_high = a.high ? 1u : 0u;
+        st.transform_threads = t;
+        st.transform_c = a.c;
+        st.transform_lds = (uint32_t)lds;
+    }
+    return le;
 }
 
 hipError_t launch_rs16_matrix(const Rs16MatArgs &a, hipStream_t s) {
@@ -738,7 +783,9 @@ hipError_t launch_rs16_matrix(const Rs16MatArgs &a, hipStream_t s) {
     // a resident grid (2 blocks per CU at the largest image) looping over the tiles: the image is
     // staged once per block, not once per 1,024 columns
     const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, 2048);
-    return rs16k::launch_mat_g<1>(a, grid, rs16_mat_bytes(a.k, a.rows), s);
+    const hipError_t e = rs16k::launch_mat_g<1>(a, grid, rs16_mat_bytes(a.k, a.rows), s);
+    if (e == hipSuccess) rs16_launch_stats().matrix_tiles = (uint32_t)tiles;  // the kernel's ntiles; matrix_grid: launch_mat_gkt
+    return e;
 }
 
 hipError_t launch_rs16_decode(const Rs16DecArgs &a, uint32_t segments, hipStream_t s) {

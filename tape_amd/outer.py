@@ -112,5 +112,15 @@ def decode_device_batch(k: int, n: int, chunks: list, chunk_bytes: int, d_out, s
     _check(r, "decode")
 
 
-__all__ = ["OuterCoder", "ReedSolomonCoder", "encode_device", "decode_device", "decode_device_batch", "MAX_CHUNK_BYTES", "EncodeError",
+def launch_stats() -> dict:
+    """te_outer_last_launch_stats: the kernels the calling thread's last te_outer_* call launched --
+    launches and segments per kernel (matrix, transform, low-register, decode), the instance of the
+    last launch of each, and the table cache's misses and evictions.  Host bookkeeping."""
+    st = _lib.te_outer_launch_stats()
+    _check(lib.te_outer_last_launch_stats(C.byref(st)), "decode")
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+
+__all__ = ["OuterCoder", "ReedSolomonCoder", "encode_device", "decode_device", "decode_device_batch", "launch_stats",
+           "MAX_CHUNK_BYTES", "EncodeError",
            "DecodeError", "_lib"]

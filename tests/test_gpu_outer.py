@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import rs16
-from tape_amd.outer import OuterCoder
+from tape_amd.outer import OuterCoder, launch_stats
 import tape_amd as T
 
 pytestmark = pytest.mark.gpu
@@ -17,6 +17,19 @@ SPOOL_GROUP_COUNT, TEST_K = 50, 17
 
 def make_data(n):  # outer.rs:206-208
     return bytes(i % 251 for i in range(n))
+
+
+def ran(**want):
+    """The calling thread's last te_outer_* call launched exactly `want` (te_outer_last_launch_stats):
+    launch counts not named are 0."""
+    st = launch_stats()
+    for f in ("matrix_launches", "transform_launches", "low_reg_launches", "decode_launches"):
+        want.setdefault(f, 0)
+    got = {f: st[f] for f in want}
+    assert got == want, st
+
+
+TRANSFORM_SHAPES = {(32, 64): 32, (40, 49): 16}  # (k, n) -> transform size, both high rate
 
 
 # matrix kernel shapes (rs16_matrix_kernel, image <= 80 KB, k <= 32): 4-row groups G odd / even,
@@ -28,6 +41,12 @@ def make_data(n):  # outer.rs:206-208
 def test_encode_matches_oracle(k, n, size):
     data = np.random.default_rng(k * 1000 + n + size).bytes(size)
     got = OuterCoder(k, n).encode(data)
+    if (k, n) in TRANSFORM_SHAPES:
+        ran(transform_launches=1, transform_high=1, transform_c=TRANSFORM_SHAPES[(k, n)])
+    elif (k, n) == (17, 50):
+        ran(matrix_launches=1, matrix_ptr_launches=0, matrix_g=9, matrix_kb=32)
+    else:
+        ran(matrix_launches=1, matrix_ptr_launches=0, matrix_g=(n - k + 3) // 4, matrix_kb=16 if k <= 16 else 32)
     exp = rs16.OracleOuter(k, n).encode(data)
     assert len(got) == n and got == exp
 
@@ -36,6 +55,7 @@ def test_encode_max_chunk_matches_oracle():
     k, n = TEST_K, SPOOL_GROUP_COUNT
     data = np.random.default_rng(7).bytes(k * (4 * 1024 * 1024) - 100)  # chunk = MAX_CHUNK_BYTES
     got = OuterCoder(k, n).encode(data)
+    ran(matrix_launches=1, matrix_ptr_launches=0, matrix_g=9, matrix_kb=32, matrix_tiles=2048, matrix_grid=2048)
     assert len(got[0]) == 4 * 1024 * 1024
     exp = rs16.OracleOuter(k, n).encode(data)
     assert got == exp
@@ -82,6 +102,7 @@ def test_encode_device_segments():
     d_in = torch.from_numpy(host).cuda()
     d_out = torch.zeros(segs * m * cb, dtype=torch.uint8, device="cuda")
     outer.encode_device(k, m, d_in, cb, segs, k * cb, d_out, m * cb)
+    ran(matrix_launches=1, matrix_ptr_launches=0, matrix_segments=segs, matrix_g=9, matrix_kb=32)
     torch.cuda.synchronize()
     got = d_out.cpu().numpy()
     for g in (0, segs - 1):
@@ -140,20 +161,30 @@ def test_decode_device_matches_original(k, n, present):
     dev = [torch.tensor(np.frombuffer(c, np.uint8), device="cuda") if i in keep else None for i, c in enumerate(chunks)]
     d_out = torch.empty(k * cb, dtype=torch.uint8, device="cuda")
     outer.decode_device(k, n, dev, cb, d_out)
+    if present == "data_only":
+        ran()  # copies only
+    elif k > 32:
+        ran(decode_launches=1, decode_kb=0, decode_lds=1)  # at most 9 missing: 9 x 40 tables fit the LDS
+    elif (k, present) == (17, "parity_only"):
+        ran(matrix_launches=1, matrix_ptr_launches=1, matrix_g=5, matrix_kb=32)
+    else:
+        ran(matrix_launches=1, matrix_ptr_launches=1)
     assert d_out.cpu().numpy().tobytes() == b"".join(chunks[:k])
 
 
 def test_decode_device_batch_mixed_patterns():
-    """te_outer_decode_device_batch: 12 segments of OuterCoder(17, 50) in one call, with three
-    erasure patterns among them (parity only, mixed, data only) and more segments per pattern than
-    one launch's shard pointers hold -- every segment's data chunks equal its original bytes, and
+    """te_outer_decode_device_batch: 24 segments of OuterCoder(17, 50) in one call, with three
+    erasure patterns among them (parity only, mixed, data only) and, for the parity-only pattern,
+    more segments than one launch's shard pointers hold (8 x 34 > 256: launches of 7 and 1; the
+    mixed pattern's 8 x 27 fit one) -- every segment's data chunks equal its original bytes, and
     the per-segment entry point gives the same bytes."""
     import torch
     from tape_amd import outer
     k, n = 17, 50
     rng = np.random.default_rng(99)
     segs, keeps, datas = [], [], []
-    for g in range(12):
+    nseg = 24
+    for g in range(nseg):
         data = rng.bytes(k * 64 * 300 - 5 * g)
         datas.append(data)
         chunks = OuterCoder(k, n).encode(data)
@@ -169,11 +200,12 @@ def test_decode_device_batch_mixed_patterns():
                      for i, c in enumerate(chunks)])
     cb = segs[0][keeps[0][0]].numel()
     assert all(s[kp[0]].numel() == cb for s, kp in zip(segs, keeps))
-    d_out = torch.zeros(12 * k * cb, dtype=torch.uint8, device="cuda")
+    d_out = torch.zeros(nseg * k * cb, dtype=torch.uint8, device="cuda")
     outer.decode_device_batch(k, n, segs, cb, d_out, k * cb)
+    ran(matrix_launches=3, matrix_ptr_launches=3, matrix_segments=16, matrix_kb=32)
     torch.cuda.synchronize()
     got = d_out.cpu().numpy().tobytes()
-    for g in range(12):
+    for g in range(nseg):
         want = b"".join(OuterCoder(k, n).encode(datas[g])[:k])
         assert got[g * k * cb:(g + 1) * k * cb] == want, g
         one = torch.zeros(k * cb, dtype=torch.uint8, device="cuda")

@@ -214,6 +214,31 @@ def test_encode_repair_launch_stats_before_any_call():
         assert fn(c.handle, None) == _lib.TE_ERR_INVALID_ARG
 
 
+def test_outer_launch_stats_before_any_call():
+    """te_outer_last_launch_stats is host bookkeeping of the calling thread: all zero before its
+    first te_outer_* call (read on a fresh thread), no device needed, a null argument refused; the
+    ctypes mirror has the C struct's size (20 32-bit and 4 64-bit fields, no padding)."""
+    import threading
+    from tape_amd import outer
+    assert C.sizeof(_lib.te_outer_launch_stats) == 20 * 4 + 4 * 8
+    got = {}
+
+    def fresh():
+        st = _lib.te_outer_launch_stats()
+        C.memset(C.byref(st), 0xFF, C.sizeof(st))
+        got["status"] = _lib.lib.te_outer_last_launch_stats(C.byref(st))
+        got["raw"] = bytes(st)
+        got["dict"] = outer.launch_stats()
+
+    t = threading.Thread(target=fresh)
+    t.start()
+    t.join()
+    assert got["status"] == 0 and got["raw"] == bytes(C.sizeof(_lib.te_outer_launch_stats))
+    assert set(got["dict"]) == {f for f, _ in _lib.te_outer_launch_stats._fields_}
+    assert all(v == 0 for v in got["dict"].values())
+    assert _lib.lib.te_outer_last_launch_stats(None) == _lib.TE_ERR_INVALID_ARG
+
+
 def test_recover_needs_device():
     import ctypes as C
     from tape_amd import _lib

@@ -28,7 +28,7 @@ def test_struct_fields_match_ctypes_mirror():
     rs = open(RS).read()
     for name in ("te_clay_info", "te_slice_metadata", "te_slicer_cfg", "te_geometry", "te_repair_plan_info",
                  "te_object", "te_decode_object", "te_recover_object", "te_repair_object", "te_decode_launch_stats",
-                 "te_encode_launch_stats", "te_repair_launch_stats"):
+                 "te_encode_launch_stats", "te_repair_launch_stats", "te_outer_launch_stats"):
         body = re.search(r"pub struct %s \{(.*?)\n\}" % name, rs, flags=re.S).group(1)
         fields = re.findall(r"pub (\w+):", body)
         mirror = [f[0] for f in getattr(_lib, name)._fields_]
