@@ -414,6 +414,71 @@ int te_decode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
                            const te_decode_object *objs, const uint8_t *h_meta, size_t nobj,
                            uint8_t *d_out, void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ranged reads: the bytes [start, start + len) of an object from its slices.  The gateway answers
+ * S3 Range requests (network/gateway/src/http/handlers/object/response.rs:45-173) and serves a
+ * multi-track object with a {skip, take} per chunk (object/manifest.rs:35-52 chunk_range_plan) by
+ * decoding each touched track in full and slicing the bytes afterwards (routes.rs:90-91,
+ * response.rs:167-169).  Stripes are independent (slicer.rs:333-361), so the engine touches only
+ * the stripes s0 = start / S .. s1 = (start + len - 1) / S of the window; each one is either
+ *   TE_RANGE_COPY    every data chunk the window intersects is a present slice's (te_shard_to_slice
+ *                    under the call's rotation, from avail_mask itself): its bytes are gathered
+ *                    straight from the slices, nothing is decoded;
+ *   TE_RANGE_DECODE  anything else: the stripe is decoded as in the full call (same pattern) and
+ *                    only the window's bytes [lo, hi) of the stripe are stored.
+ * Meaning: Slicer::decode (slicer.rs:298-364) followed by bytes[start..start + len]; start = 0,
+ * len = blob_len is byte-identical to the full decode.  start + len > blob_len (or an overflow) is
+ * TE_ERR_INVALID_ARG; len == 0 is valid and writes nothing; fewer than k present slices is
+ * TE_ERR_NOT_ENOUGH_SLICES even for a copy-only window (the reference decodes first).  The
+ * per-pattern kernels of te_clay_set_decode_jit are not used by ranged calls.
+ * Verified ranged reads are not offered: a leaf commits to a whole slice, so checking it costs the
+ * whole slice's SHA-256 whatever the window.  A caller runs te_verify_leaves_device (or keeps a
+ * verified mask per track) and passes the good mask as avail_mask.
+ * ------------------------------------------------------------------------------------------ */
+#define TE_RANGE_COPY 0
+#define TE_RANGE_DECODE 1
+/* Host only: the plan of a ranged read of an object of blob_len bytes encoded by this coder
+ * (geometry as te_slicer_geometry).  *first_stripe = s0, *nstripes = touched stripes (0 for
+ * len == 0); for touched stripe i (stripe s0 + i): classes[i], and the window [lo[i], hi[i]) in
+ * stripe bytes.  classes / lo / hi may each be NULL, else hold *nstripes entries
+ * (<= te_num_stripes).  Works for every profile and without a device. */
+int te_slicer_range_plan(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
+                         uint64_t start, uint64_t len, uint64_t *first_stripe, uint64_t *nstripes,
+                         uint32_t *classes, uint64_t *lo, uint64_t *hi);
+typedef struct te_decode_range_object {  /* te_decode_object plus the window */
+    uint64_t slices_off;  /* slice i at d_slices + slices_off + i*slice_len */
+    uint64_t slice_len;
+    uint32_t avail_mask;  /* bit i set = slice i present */
+    uint32_t pad_;
+    uint64_t out_off;     /* the window's len bytes at d_out + out_off (any byte alignment) */
+    uint64_t start, len;  /* object bytes [start, start + len) */
+} te_decode_range_object;
+/* Batched ranged read, mirroring te_decode_batch_device (one object per chunk_range_plan entry:
+ * {skip, take} = {start, len}).  Exactly len bytes are written per object.  Kernel selection counts
+ * the call's decode stripes, not the objects' stripes; the copy stripes of the whole call are one
+ * gather launch.  Enqueued on hip_stream; returns without waiting. */
+int te_decode_range_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                 const te_decode_range_object *objs, const uint8_t *h_meta, size_t nobj,
+                                 uint8_t *d_out, void *hip_stream);
+/* The per-call host form beside te_slicer_decode (the single-track object_response_ranged,
+ * routes.rs:90-91): out gets the window's len bytes (cap >= len), *out_len = len.  Only the
+ * touched stripes' chunks [s*cs, (s+1)*cs) of the slices each stripe's decode reads are staged to
+ * the device (a copy stripe: only the present data-chunk bytes it reads); the metadata suffix is
+ * read on the host.  A page-locked `out` is written by the kernels directly.  (GPU) */
+int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
+                           uint64_t start, uint64_t len, uint8_t *out, size_t cap, size_t *out_len);
+/* The handle's last ranged call (diagnostics; zeroed when such a call has passed its argument
+ * checks; te_clay_decode_launch_stats reports which decode kernels ran for its decode stripes). */
+typedef struct te_range_launch_stats {
+    uint64_t stripes_touched;  /* = stripes_decoded + stripes_copied */
+    uint64_t stripes_decoded;
+    uint64_t stripes_copied;
+    uint64_t gather_jobs;      /* chunk pieces the one gather launch copied */
+    uint64_t bytes_staged;     /* te_slicer_decode_range: slice bytes staged for the device; 0 for
+                                  the device form */
+} te_range_launch_stats;
+int te_clay_range_launch_stats(te_clay *c, te_range_launch_stats *out);
+
 typedef struct te_repair_object {
     const te_repair_plan *plan;
     uint64_t helper_off[TE_GROUP_SIZE]; /* extract_repair_data output of slice i at d_helpers+off */

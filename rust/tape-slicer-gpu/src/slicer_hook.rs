@@ -99,6 +99,57 @@ impl ClayCoder {
             (out, rejected)
         })
     }
+
+    /// A ranged object read -- Slicer::decode (slicer.rs:298-364) then `bytes[start..start + len]`,
+    /// what the gateway's object_response_ranged does per track (routes.rs:90-91, response.rs:167-169)
+    /// -- in one te_slicer_decode_range, which touches only the window's stripes.  A multi-track
+    /// read passes each chunk_range_plan entry's {skip, take} (object/manifest.rs:35-52).
+    pub fn decode_range(&mut self, cfg: &ObjectCfg, slices: &[(usize, &[u8])], start: u64, len: u64)
+                        -> Result<Vec<u8>, DecodeError> {
+        if slices.len() < self.k { return Err(DecodeError::NotEnoughSlices) }
+        let slen = slices[0].1.len();
+        let mut ptrs = vec![std::ptr::null::<u8>(); self.n()];
+        for (i, s) in slices {
+            if *i >= self.n() || s.len() != slen { return Err(DecodeError::InvalidLayout) }
+            ptrs[*i] = s.as_ptr();
+        }
+        let mut out = vec![0u8; len as usize];
+        let mut got = 0usize;
+        let c = cfg.ffi();
+        let r = unsafe {
+            ffi::te_slicer_decode_range(self.raw.as_ptr(), &c, ptrs.as_ptr(), slen, start, len, out.as_mut_ptr(), out.len(),
+                                        &mut got)
+        };
+        decode_status(r).map(|_| {
+            out.truncate(got);
+            out
+        })
+    }
+
+    /// The plan of such a read (te_slicer_range_plan, host only): the first touched stripe and, per
+    /// touched stripe, (class, lo, hi) -- TE_RANGE_COPY or TE_RANGE_DECODE and the window in stripe bytes.
+    pub fn range_plan(&self, cfg: &ObjectCfg, blob_len: u64, avail_mask: u32, start: u64, len: u64)
+                      -> Result<(u64, Vec<(u32, u64, u64)>), DecodeError> {
+        let mut g = ffi::te_geometry { stripe_size: 0, num_stripes: 0, chunk_size: 0, sub_chunk_size: 0, slice_len: 0 };
+        unsafe { ffi::te_slicer_geometry(self.raw.as_ptr(), blob_len as usize, &mut g) };
+        let ns = g.num_stripes.max(1) as usize;
+        let (mut first, mut cnt) = (0u64, 0u64);
+        let (mut cls, mut lo, mut hi) = (vec![0u32; ns], vec![0u64; ns], vec![0u64; ns]);
+        let c = cfg.ffi();
+        let r = unsafe {
+            ffi::te_slicer_range_plan(self.raw.as_ptr(), &c, blob_len, avail_mask, start, len, &mut first, &mut cnt,
+                                      cls.as_mut_ptr(), lo.as_mut_ptr(), hi.as_mut_ptr())
+        };
+        decode_status(r).map(|_| (first, (0..cnt as usize).map(|i| (cls[i], lo[i], hi[i])).collect()))
+    }
+
+    /// Stripe outcomes of the handle's last ranged read (te_clay_range_launch_stats).
+    pub fn range_launch_stats(&mut self) -> ffi::te_range_launch_stats {
+        let mut st = ffi::te_range_launch_stats { stripes_touched: 0, stripes_decoded: 0, stripes_copied: 0, gather_jobs: 0,
+                                                   bytes_staged: 0 };
+        unsafe { ffi::te_clay_range_launch_stats(self.raw.as_ptr(), &mut st) };
+        st
+    }
 }
 
 /// RepairPlan (repair.rs:16-28) with the reference's public fields, read back from the library's

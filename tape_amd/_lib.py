@@ -68,6 +68,19 @@ class te_decode_object(C.Structure):
                 ("pad_", C.c_uint32), ("out_off", C.c_uint64)]
 
 
+class te_decode_range_object(C.Structure):
+    _fields_ = [("slices_off", C.c_uint64), ("slice_len", C.c_uint64), ("avail_mask", C.c_uint32),
+                ("pad_", C.c_uint32), ("out_off", C.c_uint64), ("start", C.c_uint64), ("len", C.c_uint64)]
+
+
+class te_range_launch_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("stripes_touched", "stripes_decoded", "stripes_copied", "gather_jobs",
+                                          "bytes_staged")]
+
+
+RANGE_COPY, RANGE_DECODE = 0, 1  # TE_RANGE_COPY / TE_RANGE_DECODE
+
+
 class te_recover_object(C.Structure):
     _fields_ = [("slices_off", C.c_uint64), ("slice_len", C.c_uint64), ("avail_mask", C.c_uint32),
                 ("lost", C.c_uint32), ("out_off", C.c_uint64)]
@@ -208,6 +221,12 @@ def _load() -> C.CDLL:
         "te_host_unregister": (i, [vp]),
         "te_decode_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_decode_object), u8p, sz,
                                        vp, vp]),
+        "te_slicer_range_plan": (i, [vp, C.POINTER(te_slicer_cfg), u64, u32, u64, u64, C.POINTER(u64), C.POINTER(u64),
+                                     u32p, C.POINTER(u64), C.POINTER(u64)]),
+        "te_decode_range_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_decode_range_object), u8p,
+                                             sz, vp, vp]),
+        "te_slicer_decode_range": (i, [vp, C.POINTER(te_slicer_cfg), pp, sz, u64, u64, u8p, sz, szp]),
+        "te_clay_range_launch_stats": (i, [vp, C.POINTER(te_range_launch_stats)]),
         "te_repair_batch_device": (i, [vp, vp, C.POINTER(te_repair_object), sz, vp, vp]),
         "te_recover_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_object), u8p, sz,
                                         vp, vp]),

@@ -198,6 +198,32 @@ def decode_batch(slicer: Slicer, slices, objs, metas: bytes, out, stream=None) -
     _check(r, "decode")
 
 
+def decode_range_descs(objs: list[tuple[int, int, int, int, int, int]]):
+    """Prepared te_decode_range_object array for decode_range_batch (build once, reuse)."""
+    return (_lib.te_decode_range_object * len(objs))(
+        *[_lib.te_decode_range_object(o[0], o[1], o[2], 0, o[3], o[4], o[5]) for o in objs])
+
+
+def decode_range_batch(slicer: Slicer, slices, objs, metas: bytes, out, stream=None) -> None:
+    """te_decode_range_batch_device: bytes [start, start + len) of each object (the gateway's ranged
+    reads, one object per chunk_range_plan {skip, take}).  objs: (slices_off, slice_len, avail_mask,
+    out_off, start, len), or decode_range_descs(...) of them; exactly len bytes land at out_off.
+    metas: nobj*48 metadata bytes (host)."""
+    arr = objs if _is_desc(objs) else decode_range_descs(objs)
+    cfg = slicer._cfg()
+    mb = (C.c_uint8 * max(1, len(metas))).from_buffer_copy(metas if metas else b"\0")
+    r = lib.te_decode_range_batch_device(slicer.coder.handle, C.byref(cfg), C.c_void_p(slices.data_ptr()), arr, mb,
+                                         len(arr), C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+    _check(r, "decode")
+
+
+def range_launch_stats(coder: ClayCoder) -> dict:
+    """te_clay_range_launch_stats: the stripe outcomes of the handle's last ranged call."""
+    st = _lib.te_range_launch_stats()
+    _check(lib.te_clay_range_launch_stats(coder.handle, C.byref(st)), "decode")
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+
 def recover_batch(slicer: Slicer, slices, objs: list[tuple[int, int, int, int, int]], metas: bytes, out,
                   stream=None) -> None:
     """Node recover (recover.rs:411-442 `reconstruct`) on the device: objs are (slices_off,

@@ -32,6 +32,7 @@ struct Job {  // layout of kernels.hpp GpeJob
     u8 *out;
     u64 in_len, out_len;
     u32 rot, pattern;
+    u64 out_lo;  // always 0 here: a windowed job never runs a per-pattern kernel
 };
 struct Args {
     const Job *jobs;

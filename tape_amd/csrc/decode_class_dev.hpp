@@ -12,6 +12,10 @@
 #include "gf_dev.hpp"
 #include "dev_io.hpp"
 
+#ifndef TEC_DCLS_WINDOW
+#define TEC_DCLS_WINDOW 1  // 1: CTile's output stores honour GpeJob::out_lo (the decode classes 0..7)
+#endif
+
 namespace tec {
 namespace dcls {
 
@@ -46,7 +50,7 @@ struct CTile {
     static constexpr u32 RS = G * 256u;  // LDS / scratch row stride (G waves x 64 lanes x 4 B)
     u8 *lds8;
     cPat *pat;
-    u32 lane, col_local, vcol, sc, olen, rot, n, in_stride, out_stride, wv;
+    u32 lane, col_local, vcol, sc, olen, olo, rot, n, in_stride, out_stride, wv;
     bool full;
     __amdgpu_buffer_rsrc_t rs_in, rs_out, rs_scr;
 
@@ -71,9 +75,20 @@ struct CTile {
         const u32 col = w * 4u;
         vcol = col + 4u > a.sc ? a.sc - 4u : col;  // the row's last 4 bytes for a word past the sub-chunk
         rs_in = __builtin_amdgcn_make_buffer_rsrc((void *)J.in, 0, (int)(u32)(a.n * a.in_stride), 0x00020000);
-        olen = (u32)J.out_len;
-        full = olen >= a.out_full;  // every output row inside the job's output share (not a last stripe)
-        rs_out = __builtin_amdgcn_make_buffer_rsrc((void *)J.out, 0, (int)olen, 0x00020000);
+        // Ranged decode: the job's window is [out_lo, out_len) of the stripe's output (out_lo = 0:
+        // the whole share).  The output buffer starts AT the window -- base out + out_lo, range
+        // out_len - out_lo -- and every output offset is taken relative to it (out_base subtracts
+        // out_lo once per node, in scalar code): an offset below the window wraps past the range,
+        // so the buffer range check drops a store below out_lo exactly as it drops one past
+        // out_len, and a job without a window pays the same two compares per store as before
+        // (out_st_oob; a windowed stripe pays a third for each word outside its window).  The
+        // node-recover classes never run a windowed job and are built with TEC_DCLS_WINDOW=0
+        // (Makefile, scripts/build_class_var.sh).
+        olo = TEC_DCLS_WINDOW ? (u32)J.out_lo : 0u;
+        olen = (u32)J.out_len - olo;
+        // every output row inside the job's output share (not a last stripe, not a window)
+        full = (u32)J.out_len >= a.out_full && olo == 0;
+        rs_out = __builtin_amdgcn_make_buffer_rsrc((void *)(J.out + olo), 0, (int)olen, 0x00020000);
         const u32 nscr = a.nscratch ? a.nscratch : 1u;
         rs_scr = __builtin_amdgcn_make_buffer_rsrc(a.scratch + (u64)tile * nscr * RS, 0, (int)(nscr * RS), 0x00020000);
     }
@@ -109,10 +124,12 @@ struct CTile {
     }
     // output base of column-0 node `node`: its data chunk, or for a parity node an offset past
     // every stripe's output range, so the buffer range check drops its stores
-    __device__ __forceinline__ u32 out_base(u32 node) const { return node < kData ? node * out_stride : kDropBase; }
-    static constexpr u32 kData = 7, kDropBase = 0x80000000u;
+    // (relative to the window's start, see the constructor)
+    __device__ __forceinline__ u32 out_base(u32 node) const { return node < kData ? node * out_stride - olo : kDropBase; }
+    static constexpr u32 kData = 7, kDropBase = 0x80000000u, kBelow = 0xFFFFFFFDu;
     // one decoded word to data chunk offset `ob` at plane offset `po`, where it was loaded; a
-    // word across the end of the stripe's output share is written byte by byte
+    // word that is not wholly inside the output range -- across the end of the stripe's share, or
+    // across either end of a ranged decode's window -- is written byte by byte
     __device__ __forceinline__ void out_st(u32 ob, u32 po, u32 v) const {
         if (ob == kDropBase) return;  // uniform: a column-0 parity node's row is not output
         out_st_oob(ob, po, v);
@@ -123,12 +140,15 @@ struct CTile {
         const u32 o = ob + po + vcol;
         if (full) {  // uniform: every data row of the stripe lies inside its output share
             __builtin_amdgcn_raw_buffer_store_b32(v, rs_out, (int)o, 0, 2);
-        } else if (o + 4u > olen && o < olen) {
+        } else if (o < olen && o + 3u < olen) {  // (an offset below the window has wrapped: outside)
+            __builtin_amdgcn_raw_buffer_store_b32(v, rs_out, (int)o, 0, 2);
+        } else if (o < olen || o >= kBelow) {
+            // across the range's end, or across the window's start (the word begins 1..3 bytes
+            // below it: its offset wrapped to >= kBelow): each byte passes or fails the range check
+            // on its own, both bounds at once
 #pragma unroll
             for (u32 k = 0; k < 4u; k++) __builtin_amdgcn_raw_buffer_store_b8((u8)(v >> (8u * k)), rs_out, (int)(o + k), 0, 0);
-        } else {
-            __builtin_amdgcn_raw_buffer_store_b32(v, rs_out, (int)o, 0, 2);
-        }
+        }  // else: wholly past the end, wholly below the window, or a dropped row: nothing to write
     }
     // The matrix of one erased row: the pattern pointer is laundered each time so the row's table
     // loads are issued where they are used, not hoisted over the straight-line program (the

@@ -157,16 +157,19 @@ __global__ void __launch_bounds__(G * 64, WPL > 1 ? TEC_DEC_WPE_WIDE : TEC_DEC_W
     };
     // the stripe's output share ends at out_len, possibly inside a data row (the last chunk's
     // padding, or the next stripe's share): a block across that end is written byte by byte
-    const uint32_t olen = (uint32_t)J.out_len;
+    // a ranged decode's window starts at out_lo (0: the whole share): nothing below it is
+    // written, and a block or word across it is written byte by byte like one across out_len
+    const uint32_t olen = (uint32_t)J.out_len, olo = (uint32_t)J.out_lo;
     auto flush16 = [&](const uint8_t *row, uint32_t b, uint32_t off) {  // block b of the row
         const uint32_t vo = blk_off(b), lo = vo == kDrop ? 0u : vo;
         const u32x4 v = *reinterpret_cast<const u32x4 *>(row + lo);
-        if (vo == kDrop || off + vo + 16u <= olen) {
+        if (vo == kDrop || (off + vo + 16u <= olen && off + vo >= olo)) {
             __builtin_amdgcn_raw_buffer_store_b128(v, rs_out, (int)vo, (int)off, TEC_DEC_ST_AUX);
         } else {
 #pragma unroll
             for (uint32_t b = 0; b < 16u; b++)  // bytes past out_len fail the range check
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(v[b >> 2] >> (8u * (b & 3u))), rs_out, (int)(vo + b), (int)off, 0);
+                if (off + vo + b >= olo)
+                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(v[b >> 2] >> (8u * (b & 3u))), rs_out, (int)(vo + b), (int)off, 0);
         }
     };
 
@@ -243,12 +246,13 @@ __global__ void __launch_bounds__(G * 64, WPL > 1 ? TEC_DEC_WPE_WIDE : TEC_DEC_W
     // load column vcol; a row across the stripe's output share is written byte by byte there
     auto put_out = [&](uint32_t off, uint32_t wv_, int k) {
         if (off == kDrop) return;
-        if (off + sc <= olen) {
+        if (off + sc <= olen && off >= olo) {  // uniform: the row lies inside [out_lo, out_len)
             __builtin_amdgcn_raw_buffer_store_b32(wv_, rs_out, (int)vcol[k], (int)off, TEC_DEC_ST_AUX);
-        } else {
+        } else if (off + sc > olo) {  // uniform: a row wholly below the window is not written
 #pragma unroll
             for (uint32_t b = 0; b < 4u; b++)  // bytes past out_len fail the range check
-                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(wv_ >> (8u * b)), rs_out, (int)(vcol[k] + b), (int)off, 0);
+                if (off + vcol[k] + b >= olo)
+                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(wv_ >> (8u * b)), rs_out, (int)(vcol[k] + b), (int)off, 0);
         }
     };
 
@@ -486,10 +490,12 @@ __global__ void __launch_bounds__(G * 64, WPL > 1 ? TEC_DEC_WPE_WIDE : TEC_DEC_W
             if (!wide_tail) {
                 const uint32_t lt_off = nb * 16u + lane * 2u, vot = lane < (tail >> 1) ? lt_off : kDrop;
                 const uint16_t v = *reinterpret_cast<const uint16_t *>(row + lt_off);
-                if (vot == kDrop || off + vot + 2u <= olen) {
+                if (vot == kDrop || (off + vot + 2u <= olen && off + vot >= olo)) {
                     __builtin_amdgcn_raw_buffer_store_b16(v, rs_out, (int)vot, (int)off, 0);
-                } else {
-                    __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, rs_out, (int)vot, (int)off, 0);
+                } else {  // bytes past out_len fail the range check
+                    if (off + vot >= olo) __builtin_amdgcn_raw_buffer_store_b8((uint8_t)v, rs_out, (int)vot, (int)off, 0);
+                    if (off + vot + 1u >= olo)
+                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(v >> 8), rs_out, (int)(vot + 1u), (int)off, 0);
                 }
             }
         }

@@ -56,15 +56,16 @@ __device__ __forceinline__ void st_word(uint8_t *__restrict__ p, uint32_t v, uin
     }
 }
 
-// Store only the bytes of the word that fall below `limit` (byte offset bound of the output).
+// Store only the bytes of the word that fall in [lo, limit) (byte offset bounds of the output;
+// lo is non-zero only for a ranged decode's first stripe).
 __device__ __forceinline__ void st_word_trim(uint8_t *__restrict__ base, uint64_t off, uint64_t limit,
-                                             uint32_t v, uint32_t nc) {
-    if (off + nc <= limit) {
+                                             uint32_t v, uint32_t nc, uint64_t lo = 0) {
+    if (off + nc <= limit && off >= lo) {
         st_word(base + off, v, nc);
         return;
     }
     for (uint32_t i = 0; i < nc; i++)
-        if (off + i < limit) base[off + i] = (uint8_t)(v >> (8 * i));
+        if (off + i < limit && off + i >= lo) base[off + i] = (uint8_t)(v >> (8 * i));
 }
 
 // Wave-uniform access: `ub` (uniform base, SGPR) + the lane's 32-bit column offset.  `al` is the

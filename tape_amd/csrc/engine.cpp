@@ -536,6 +536,8 @@ struct te_clay {
     // the decode_enqueue launches of the last decode / recover call (te_clay_decode_launch_stats):
     // zeroed when the call starts its device work, summed over its decode_enqueue passes
     te_decode_launch_stats dls{};
+    // the last ranged call's stripe outcomes (te_clay_range_launch_stats), zeroed by its entry point
+    te_range_launch_stats rgs{};
     // the same for the encode_enqueue / repair_enqueue launches of the last encode / repair call
     te_encode_launch_stats els{};
     te_repair_launch_stats rls{};
@@ -1145,7 +1147,56 @@ struct DecItem {          // one object, host-validated
     uint64_t slice_len, blob_len, stripe, ns, cs, out_off;
     uint32_t avail;
     int32_t lost = -1;    // >= 0: output = that slice's chunks at out_off + stripe * cs (node recover)
+    // ranged read: only object bytes [w_start, w_start + w_len) are written, at out_off
+    bool ranged = false;
+    uint64_t w_start = 0, w_len = 0;
+    uint64_t in_skew = 0;  // the slices at in_base start at slice byte in_skew (te_slicer_decode_range's staging)
 };
+
+// Ranged reads (te_slicer_range_plan): the stripes a window touches, [sb, se)
+inline void range_stripes(uint64_t S, uint64_t start, uint64_t len, uint64_t &sb, uint64_t &se) {
+    sb = se = 0;
+    if (len == 0 || S == 0) return;
+    sb = start / S;
+    se = (start + len - 1) / S + 1;
+}
+// ... and the window inside stripe st, [lo, hi) in stripe bytes.  copy: every data chunk it
+// intersects (chunk x = stripe bytes [x cs, (x + 1) cs), shard x) is a present slice's -- decided
+// from the mask itself, not from the padded erasure set -- so nothing needs decoding.
+struct RangeWin { uint64_t lo, hi; bool copy; };
+RangeWin range_window(int n, int rotated, uint32_t avail, uint64_t blob_len, uint64_t S, uint64_t cs, uint64_t st,
+                      uint64_t start, uint64_t len) {
+    const uint64_t base = st * S, end = std::min({start + len, base + S, blob_len});
+    RangeWin w;
+    w.lo = start > base ? start - base : 0;
+    w.hi = end - base;
+    w.copy = true;
+    for (uint64_t x = w.lo / cs; x * cs < w.hi; x++)
+        if (!((avail >> te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)x)) & 1u)) w.copy = false;
+    return w;
+}
+// every touched stripe's window, stripe sb + i at [i]
+std::vector<RangeWin> range_windows(int n, int rotated, uint32_t avail, uint64_t blob_len, uint64_t S, uint64_t cs,
+                                    uint64_t start, uint64_t len) {
+    uint64_t sb, se;
+    range_stripes(S, start, len, sb, se);
+    std::vector<RangeWin> w;
+    for (uint64_t st = sb; st < se; st++) w.push_back(range_window(n, rotated, avail, blob_len, S, cs, st, start, len));
+    return w;
+}
+// The padded erasure set of stripe st as internal nodes: the shards whose slices are missing,
+// padded to n - k erasures (the decode then reads exactly the k nodes left).
+uint64_t stripe_emask(const ClayHost &h, int rotated, uint32_t avail, uint64_t st) {
+    uint64_t emask = 0;
+    for (int sh = 0; sh < h.n; sh++)
+        if (!((avail >> te_shard_to_slice(rotated, (uint32_t)h.n, (uint32_t)st, (uint32_t)sh)) & 1u))
+            emask |= 1ull << h.ext_to_int(sh);
+    return h.pad_erasures(emask);
+}
+// check a window against the object (the argument rules of the ranged entry points)
+inline bool range_valid(uint64_t blob_len, uint64_t start, uint64_t len) {
+    return start + len >= start && start + len <= blob_len;
+}
 
 // Validate one object like Slicer::decode (slicer.rs:298-331, validate_layout :79-105).
 int decode_validate(const te_clay *c, const uint8_t *meta48, uint64_t slice_len, uint32_t avail, DecItem &it) {
@@ -1341,18 +1392,20 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
     // compiled programs kept on the host: <= ~430 MB (26 KB per pattern, as many as the device
     // store's cap; 77,520 masks exist for k = 7, x 20 outputs for node recover)
     if (c->dec_cache.size() > std::max<size_t>(c->dstore.max_cap, nitems)) c->dec_cache.clear();
+    std::vector<std::vector<RangeWin>> wins(nitems);  // ranged items: their touched stripes' windows
     {
         std::vector<std::pair<uint64_t, int>> keys;
         std::unordered_map<uint64_t, char> seen;
         for (size_t i = 0; i < nitems; i++) {
             const DecItem &it = items[i];
-            for (uint64_t st = 0; st < it.ns; st++) {
-                uint64_t emask = 0;
-                for (int sh = 0; sh < n; sh++) {
-                    const uint32_t sl = te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)sh);
-                    if (!((it.avail >> sl) & 1u)) emask |= 1ull << h.ext_to_int(sh);
-                }
-                emask = h.pad_erasures(emask);
+            uint64_t sb = 0, se = it.ns;
+            if (it.ranged) {
+                range_stripes(it.stripe, it.w_start, it.w_len, sb, se);
+                wins[i] = range_windows(n, rotated, it.avail, it.blob_len, it.stripe, it.cs, it.w_start, it.w_len);
+            }
+            for (uint64_t st = sb; st < se; st++) {
+                if (it.ranged && wins[i][st - sb].copy) continue;
+                const uint64_t emask = stripe_emask(h, rotated, it.avail, st);
                 const int onode = it.lost >= 0 ? h.ext_to_int((int)te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st,
                                                                                       (uint32_t)it.lost)) : -1;
                 if (seen.emplace(dec_key(emask, onode), 1).second) keys.push_back({emask, onode});
@@ -1369,15 +1422,36 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
     std::map<uint64_t, std::vector<GpeJob>> groups;  // by chunk size
     std::map<uint64_t, uint64_t> group_in_stride;
     uint32_t max_er = 0;
+    // ranged reads: a copy stripe's window is gathered from the present data chunks (one launch
+    // for the call), a decode stripe's job carries its window [out_lo, out_len)
+    std::vector<CopyJob> copies;
+    bool ranged_call = false;
     for (size_t i = 0; i < nitems; i++) {
         const DecItem &it = items[i];
-        for (uint64_t st = 0; st < it.ns; st++) {
-            uint64_t emask = 0;
-            for (int sh = 0; sh < n; sh++) {
-                const uint32_t sl = te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)sh);
-                if (!((it.avail >> sl) & 1u)) emask |= 1ull << h.ext_to_int(sh);
+        uint64_t sb = 0, se = it.ns;
+        if (it.ranged) range_stripes(it.stripe, it.w_start, it.w_len, sb, se);
+        ranged_call = ranged_call || it.ranged;
+        for (uint64_t st = sb; st < se; st++) {
+            RangeWin win{0, 0, false};
+            if (it.ranged) {
+                win = wins[i][st - sb];
+                c->rgs.stripes_touched++;
+                if (win.copy) {
+                    c->rgs.stripes_copied++;
+                    for (uint64_t x = win.lo / it.cs; x * it.cs < win.hi; x++) {
+                        const uint64_t a = std::max(win.lo, x * it.cs), b = std::min(win.hi, (x + 1) * it.cs);
+                        const uint32_t sl = te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)x);
+                        CopyJob cj{};
+                        cj.src = d_slices + it.in_base + sl * it.slice_len + (st * it.cs - it.in_skew) + (a - x * it.cs);
+                        cj.dst = d_out + it.out_off + (st * it.stripe + a - it.w_start);
+                        cj.len = cj.valid = b - a;
+                        copies.push_back(cj);
+                    }
+                    continue;
+                }
+                c->rgs.stripes_decoded++;
             }
-            emask = h.pad_erasures(emask);
+            const uint64_t emask = stripe_emask(h, rotated, it.avail, st);
             const int onode = it.lost >= 0 ? h.ext_to_int((int)te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st,
                                                                                   (uint32_t)it.lost)) : -1;
             fused = fused || onode >= 0;
@@ -1396,11 +1470,17 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
                 pid = f->second;
             }
             GpeJob g{};
-            g.in = d_slices + it.in_base + st * it.cs;
+            g.in = d_slices + it.in_base + (st * it.cs - it.in_skew);
             g.in_len = ~0ull;
             if (onode >= 0) {  // the lost slice's chunk of this stripe, whole
                 g.out = d_out + it.out_off + st * it.cs;
                 g.out_len = it.cs;
+            } else if (it.ranged) {
+                // `out` stays the address of stripe byte 0: for a window's first stripe that is
+                // below the caller's range by out_lo bytes, which the kernels never store to
+                g.out = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(d_out) + it.out_off + st * it.stripe - it.w_start);
+                g.out_lo = win.lo;
+                g.out_len = win.hi;
             } else {
                 g.out = d_out + it.out_off + st * (raw ? 0 : it.stripe);
                 g.out_len = raw ? it.cs * (uint64_t)h.k : (st + 1 == it.ns ? it.blob_len - st * it.stripe : it.stripe);
@@ -1412,7 +1492,19 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
             group_in_stride[key] = it.slice_len;
         }
     }
-    if (groups.empty()) return TE_OK;
+    c->rgs.gather_jobs += copies.size();
+    if (groups.empty()) {  // nothing to decode: a ranged call of copy stripes only (or of nothing)
+        if (copies.empty()) return TE_OK;
+        Arena &A = c->dec;
+        A.img.clear();
+        const size_t off = A.put(copies.data(), copies.size() * sizeof(CopyJob));
+        int r = A.upload(s);
+        if (r) return r;
+        KTimer kt(s);
+        TE_HIP(launch_gather(A.at<CopyJob>(off), (uint32_t)copies.size(), s));
+        kt.stop();
+        return A.mark_done(s);
+    }
     // staged kernel (decode_stage.hip) when every pattern compiles to a plane program; of the two
     // row orientations the one with fewer scratch rows
     uint32_t lds_rows = 0, nscr_max = 0;
@@ -1445,7 +1537,9 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
         const char *e = tec_knob("TEC_DEC_CLASS");
         return !(e && e[0] == '0');
     }();
-    if (staged && !fused) {  // (pattern kernels write data chunks; recover's outputs are other nodes)
+    // (pattern kernels write data chunks whole: recover's outputs are other nodes, and a ranged
+    // call's jobs carry a window the pattern kernels do not clip)
+    if (staged && !fused && !ranged_call) {
         if (!c->jit) {
             c->jit = dec_jit_new(c->device);
             if (c->jit_mode >= 0) dec_jit_set(c->jit, c->jit_mode, c->jit_min);
@@ -1598,6 +1692,7 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
         if (!kv.second.empty()) offs.push_back({kv.first, A.put(kv.second.data(), kv.second.size() * sizeof(GpeJob))});
     for (Fixed &f : fixed) f.off = A.put(f.jobs.data(), f.jobs.size() * sizeof(GpeJob));
     for (ClassGrp &cg : cls) cg.off = A.put(cg.jobs.data(), cg.jobs.size() * sizeof(GpeJob));
+    const size_t copy_off = A.put(copies.data(), copies.size() * sizeof(CopyJob));
     // new store entries ride in the same upload, then move to their slots on this stream
     size_t fp_off = 0, fh_off = 0, fs_off = 0, fo_off = 0;
     if (in_store && !fill.pats.empty()) {
@@ -1714,6 +1809,7 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
     }
     uint8_t *const cls_scratch = scratch ? scratch + cls_off : nullptr;
     KTimer kt(s);
+    if (!copies.empty()) TE_HIP(launch_gather(A.at<CopyJob>(copy_off), (uint32_t)copies.size(), s));
     for (const Fixed &f : fixed) {
         const dfix_args a = fixed_args(f, scratch);
         TE_HIP(launch_dec_fixed(*f.k, a, dec_jit_geom(a.sc).G, s));
@@ -3269,6 +3365,61 @@ int te_decode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     return decode_enqueue(c, cfg, d_slices, items.data(), items.size(), d_out, (hipStream_t)stream, false);
 }
 
+int te_slicer_range_plan(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
+                         uint64_t start, uint64_t len, uint64_t *first_stripe, uint64_t *nstripes, uint32_t *classes,
+                         uint64_t *lo, uint64_t *hi) {
+    if (!c || !cfg || !first_stripe || !nstripes) return TE_ERR_INVALID_ARG;
+    const ClayHost &h = c->h;
+    if (!range_valid(blob_len, start, len)) return TE_ERR_INVALID_ARG;
+    const uint32_t avail = avail_mask & (h.n >= 32 ? 0xffffffffu : (1u << h.n) - 1u);
+    if (__builtin_popcount(avail) < h.k) return TE_ERR_NOT_ENOUGH_SLICES;
+    te_geometry g;
+    int r = te_slicer_geometry(c, (size_t)blob_len, &g);
+    if (r) return r;
+    uint64_t sb, se;
+    range_stripes(g.stripe_size, start, len, sb, se);
+    *first_stripe = sb;
+    *nstripes = se - sb;
+    for (uint64_t st = sb; st < se; st++) {
+        const RangeWin w = range_window(h.n, cfg->rotated, avail, blob_len, g.stripe_size, g.chunk_size, st, start, len);
+        if (classes) classes[st - sb] = w.copy ? TE_RANGE_COPY : TE_RANGE_DECODE;
+        if (lo) lo[st - sb] = w.lo;
+        if (hi) hi[st - sb] = w.hi;
+    }
+    return TE_OK;
+}
+
+int te_clay_range_launch_stats(te_clay *c, te_range_launch_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->rgs;
+    return TE_OK;
+}
+
+int te_decode_range_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                 const te_decode_range_object *objs, const uint8_t *h_meta, size_t nobj, uint8_t *d_out,
+                                 void *stream) {
+    if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
+    std::vector<DecItem> items(nobj);
+    for (size_t i = 0; i < nobj; i++) {
+        int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, items[i]);
+        if (r) return r;
+        if (!range_valid(items[i].blob_len, objs[i].start, objs[i].len)) return TE_ERR_INVALID_ARG;
+        items[i].in_base = objs[i].slices_off;
+        items[i].out_off = objs[i].out_off;
+        items[i].ranged = true;
+        items[i].w_start = objs[i].start;
+        items[i].w_len = objs[i].len;
+    }
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->rgs = te_range_launch_stats{};
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    return decode_enqueue(c, cfg, d_slices, items.data(), items.size(), d_out, (hipStream_t)stream, false);
+}
+
 int te_repair_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair_object *objs, size_t nobj,
                            uint8_t *d_out, void *stream) {
     if (!c || (!objs && nobj)) return TE_ERR_INVALID_ARG;
@@ -3718,6 +3869,102 @@ int te_slicer_decode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const 
     r = decode_enqueue(c, cfg, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, false);
     if (r) return r;
     TE_HIP(hipMemcpyAsync(out, c->io_out.p, it.blob_len, hipMemcpyDeviceToHost, c->stream));
+    TE_HIP(hipStreamSynchronize(c->stream));
+    return TE_OK;
+}
+
+int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
+                           uint64_t start, uint64_t len, uint8_t *out, size_t cap, size_t *out_len) {
+    if (!c || !cfg || !slices) return TE_ERR_INVALID_ARG;
+    const ClayHost &h = c->h;
+    const int n = h.n;
+    uint32_t avail = 0;
+    int first = -1;
+    for (int i = 0; i < n; i++)
+        if (slices[i]) { avail |= 1u << i; if (first < 0) first = i; }
+    if (first < 0) return TE_ERR_NOT_ENOUGH_SLICES;
+    if (slice_len < TE_META_SIZE) return TE_ERR_INVALID_LAYOUT;
+    DecItem it{};
+    int r = decode_validate(c, slices[first] + slice_len - TE_META_SIZE, slice_len, avail, it);
+    if (r) return r;
+    if (!range_valid(it.blob_len, start, len)) return TE_ERR_INVALID_ARG;
+    if (out_len) *out_len = (size_t)len;
+    if (len && (!out || cap < len)) return TE_ERR_BUFFER_TOO_SMALL;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->rgs = te_range_launch_stats{};
+    if (len == 0) return TE_OK;
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    r = ensure_stream(c);
+    if (r) return r;
+    // The staging holds, per slice, only the touched stripes' chunks: slice i's bytes
+    // [sb cs, se cs) at i * T.  Of those, a decode stripe stages the chunks of the k slices its
+    // (padded) pattern reads, a copy stripe the present data-chunk bytes inside the window.
+    uint64_t sb, se;
+    range_stripes(it.stripe, start, len, sb, se);
+    const uint64_t T = (se - sb) * it.cs;
+    const int rotated = cfg->rotated;
+    struct Piece { uint64_t at; const uint8_t *src; uint64_t len; };  // staging offset <- slice bytes
+    std::vector<Piece> pieces;
+    auto stage = [&](uint32_t sl, uint64_t from, uint64_t bytes) {  // slice bytes [from, from + bytes)
+        const uint64_t at = sl * T + (from - sb * it.cs);
+        if (!pieces.empty() && pieces.back().at + pieces.back().len == at && pieces.back().src + pieces.back().len == slices[sl] + from)
+            pieces.back().len += bytes;  // the next stripe's chunk of the same slice
+        else
+            pieces.push_back({at, slices[sl] + from, bytes});
+        c->rgs.bytes_staged += bytes;
+    };
+    const std::vector<RangeWin> wins = range_windows(n, rotated, avail, it.blob_len, it.stripe, it.cs, start, len);
+    std::vector<uint64_t> emasks(wins.size(), 0);  // the decode stripes' padded erasure sets
+    for (size_t i = 0; i < wins.size(); i++)
+        if (!wins[i].copy) emasks[i] = stripe_emask(h, rotated, avail, sb + i);
+    for (int sl = 0; sl < n; sl++) {  // slice-major, so a slice's consecutive chunks merge into one piece
+        if (!slices[sl]) continue;
+        for (uint64_t st = sb; st < se; st++) {
+            const uint32_t sh = te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)sl);
+            const RangeWin &w = wins[st - sb];
+            if (w.copy) {
+                const uint64_t a = std::max(w.lo, sh * it.cs), b = std::min(w.hi, (sh + 1) * it.cs);
+                if ((int)sh < h.k && a < b) stage((uint32_t)sl, st * it.cs + (a - sh * it.cs), b - a);
+            } else if (!((emasks[st - sb] >> h.ext_to_int((int)sh)) & 1ull)) {
+                stage((uint32_t)sl, st * it.cs, it.cs);
+            }
+        }
+    }
+    it.in_base = 0;
+    it.in_skew = sb * it.cs;
+    it.slice_len = T;  // the stride between the staged slices
+    it.out_off = 0;
+    it.ranged = true;
+    it.w_start = start;
+    it.w_len = len;
+    const size_t total = (size_t)n * T;
+    TE_HIP(c->hio_in.ensure(total));
+    std::vector<tec::CopyPool::Seg> segs;
+    for (const Piece &p : pieces) segs.push_back({c->hio_in.u8() + p.at, p.src, (size_t)p.len});
+    copy_pool(c->device).run(segs);
+    // few stripes: the kernels read the page-locked staging and write a page-locked `out` over
+    // PCIe, as te_slicer_decode does; more: the staged pieces go to device memory first
+    if (se - sb <= kDecSmallStripes) {
+        uint8_t *const d_out = host_device_ptr(out);
+        if (!d_out) TE_HIP(c->hio_out.ensure(len));
+        uint8_t *dst = d_out ? d_out : c->hio_out.u8();
+        r = decode_enqueue(c, cfg, c->hio_in.u8(), &it, 1, dst, c->stream, false);
+        if (r) return r;
+        TE_HIP(hipStreamSynchronize(c->stream));
+        if (!d_out) copy_pool(c->device).run({{out, c->hio_out.p, (size_t)len}});
+        c->dls.direct_out = d_out ? 1u : 0u;
+        return TE_OK;
+    }
+    TE_HIP(c->io_in.ensure(total));
+    TE_HIP(c->io_out.ensure(len));
+    for (const Piece &p : pieces)
+        TE_HIP(hipMemcpyAsync(c->io_in.as<uint8_t>() + p.at, c->hio_in.u8() + p.at, p.len, hipMemcpyHostToDevice, c->stream));
+    r = decode_enqueue(c, cfg, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, false);
+    if (r) return r;
+    TE_HIP(hipMemcpyAsync(out, c->io_out.p, len, hipMemcpyDeviceToHost, c->stream));
     TE_HIP(hipStreamSynchronize(c->stream));
     return TE_OK;
 }

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(kGpeWords * kGpePlaneThreads) gpe_kernel(GpeAr
         if (e < 0) return;
         uint32_t side = (uint32_t)e;
         if (a.out_rotated) { side += J.rot; side = side >= a.n ? side - a.n : side; }
-        st_word_trim(J.out, (uint64_t)side * a.out_stride + (uint64_t)z * sc + wp.c, J.out_len, v, wp.nc);
+        st_word_trim(J.out, (uint64_t)side * a.out_stride + (uint64_t)z * sc + wp.c, J.out_len, v, wp.nc, J.out_lo);
     };
     auto slot = [&](uint32_t *base, uint32_t e, uint32_t z) -> uint32_t & {
         return base[((size_t)e * alpha + z) * kGpeWords + wi];

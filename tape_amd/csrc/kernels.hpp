@@ -131,6 +131,8 @@ struct GpeJob {
     uint64_t out_len;      // output bytes kept from `out` (trim beyond)
     uint32_t rot;          // rotation offset for the rotated side
     uint32_t pattern;      // index into the pattern array
+    uint64_t out_lo;       // ranged decode: output bytes below this offset from `out` are not written
+                           // (the window [out_lo, out_len) of the stripe; 0 everywhere else)
 };
 
 struct GpeArgs {

@@ -604,6 +604,41 @@ class Slicer:
         _check(r, "decode")
         return bytes(out)[:got.value]
 
+    def decode_range(self, chunks: list[tuple[int, bytes]], start: int, length: int) -> bytes:
+        """te_slicer_decode_range: Slicer::decode followed by bytes[start..start + length] (the
+        gateway's object_response_ranged, routes.rs:90-91), touching only the window's stripes."""
+        if not chunks:
+            raise DecodeError("NotEnoughSlices")
+        n = self.n()
+        slice_len = len(chunks[0][1])
+        ptrs = (C.c_void_p * n)()
+        keep = []
+        for idx, data in chunks:
+            if not (0 <= idx < n) or len(data) != slice_len:
+                raise DecodeError("InvalidLayout")
+            b = _buf(data)
+            keep.append(b)
+            ptrs[idx] = C.cast(b, C.c_void_p)
+        out = (C.c_uint8 * max(1, length))()
+        got = C.c_size_t()
+        cfg = self._cfg()
+        r = lib.te_slicer_decode_range(self.coder.handle, C.byref(cfg), ptrs, slice_len, start, length, out,
+                                       len(out), C.byref(got))
+        _check(r, "decode")
+        return bytes(out)[:got.value]
+
+    def range_plan(self, blob_len: int, avail_mask: int, start: int, length: int):
+        """te_slicer_range_plan (host only): (first_stripe, [(class, lo, hi) per touched stripe]),
+        class _lib.RANGE_COPY or _lib.RANGE_DECODE, [lo, hi) the window in stripe bytes."""
+        ns = max(1, int(self.geometry(blob_len).num_stripes))
+        first, cnt = C.c_uint64(), C.c_uint64()
+        cls, lo, hi = (C.c_uint32 * ns)(), (C.c_uint64 * ns)(), (C.c_uint64 * ns)()
+        cfg = self._cfg()
+        r = lib.te_slicer_range_plan(self.coder.handle, C.byref(cfg), blob_len, avail_mask, start, length,
+                                     C.byref(first), C.byref(cnt), cls, lo, hi)
+        _check(r, "decode")
+        return int(first.value), [(int(cls[i]), int(lo[i]), int(hi[i])) for i in range(cnt.value)]
+
     def decode_verified(self, chunks: list[tuple[int, bytes]], leaves) -> tuple[bytes, list[int]]:
         """Slicer::decode behind the gateway's check (network/gateway/src/http/handlers/object/
         decode.rs:121-139): a slice enters the decode only if hash_leaf(slice) == leaves[index].
