@@ -621,6 +621,93 @@ int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_
                               uint32_t *rejected_mask);
 
 /* ------------------------------------------------------------------------------------------
+ * Host read pipeline: the read side's host boundary, the counterpart of te_encode_batch_host /
+ * te_encode_commit_batch_host / te_stream_writer_*.  Every reader of the reference holds its
+ * slices in host memory: BlobDecoder::decode in the SDK's read_track, and the gateway's
+ * decode_track_bytes (network/gateway/src/http/handlers/object/decode.rs:28-91), one call per
+ * track of a multi-track object.  All pointers below are HOST pointers; offsets in `objs` are
+ * relative to h_slices / h_out.
+ * ------------------------------------------------------------------------------------------ */
+/* Host only: the windows the read pipeline cuts a batch into.  cuts[0..*nwindows] (*nwindows + 1
+ * entries): window w holds objects [cuts[w], cuts[w+1]); contiguous, covering, in object order.
+ * A window holds at most window_bytes (0 = 128 MiB), counted per object as its present slices'
+ * bytes in (popcount(avail_mask) * slice_len) plus its blob_len out (from its metadata suffix in
+ * h_meta); an object larger than that gets a window of its own.  *nwindows is always set (0 for
+ * nobj == 0); cuts == NULL returns the count only, fewer than *nwindows + 1 entries (`cap`) is
+ * TE_ERR_BUFFER_TOO_SMALL.  A suffix that does not parse is that suffix's error.  Works without a
+ * device. */
+int te_decode_window_plan(const te_clay *c, const te_decode_object *objs, const uint8_t *h_meta, size_t nobj,
+                          size_t window_bytes, size_t *cuts, size_t cap, size_t *nwindows);
+/* Batched Slicer::decode HOST -> HOST: te_decode_batch_device's meaning for slices in host memory.
+ * Only the slices named in avail_mask are read from h_slices and uploaded (absent slots may be
+ * unmapped); exactly blob_len bytes are written per object at h_out + out_off.  The windows of
+ * te_decode_window_plan run over three streams, so the H2D copy of window w+1, the kernels of w
+ * and the D2H copy of w-1 overlap.  h_slices / h_out should be pinned (te_host_alloc /
+ * te_host_register) for full PCIe rate.  Every object is validated before anything is enqueued.
+ * Synchronous. */
+int te_decode_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_decode_object *objs,
+                         const uint8_t *h_meta, size_t nobj, uint8_t *h_out, size_t window_bytes);
+/* The gateway's object read (decode.rs:121-139) HOST -> HOST, with te_decode_verified_batch_device's
+ * contract: every present slice is checked against h_leaves (nobj * n * 32 bytes),
+ * h_rejected_mask[o] (or NULL) = the present slices that failed, an object with at least k verified
+ * slices decodes from them (h_status[o] = TE_OK), any other gets TE_ERR_NOT_ENOUGH_SLICES and
+ * nothing is written to its output range.  h_status: nobj ints, required.  Any slice_len.
+ * The leaf hashes follow te_set_commit_hashing, per window:
+ *   TE_HASH_HOST    the host pool hashes the slices in the caller's buffer before the upload; only
+ *                   the verified slices of objects that decode are uploaded, and the host never
+ *                   waits for the device inside the pipeline;
+ *   TE_HASH_DEVICE  every present slice is uploaded and hashed by the leaf-verify kernel; the host
+ *                   waits once per window for the masks, after it has enqueued the upload of the
+ *                   next window (a window with a slice_len that is no multiple of 4 is hashed on
+ *                   the host);
+ *   TE_HASH_AUTO    whichever the stream writer's rule picks for the window's slice count and
+ *                   lengths.
+ * Outputs, masks and statuses are identical in every mode.  Synchronous. */
+int te_decode_verified_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices,
+                                  const te_decode_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                  size_t nobj, uint8_t *h_out, uint32_t *h_rejected_mask, int *h_status,
+                                  size_t window_bytes);
+/* Ordered, asynchronous window submission for reads: the counterpart of te_stream_writer_*.
+ *   te_stream_reader_new: over ncoders device-bound handles; window t goes to handle
+ *     (t - 1) mod ncoders.  The reader owns its device buffers and a host thread per handle, and
+ *     runs on the handles' own streams; the handles must outlive it and must not be re-bound
+ *     meanwhile.  It copies the process's te_set_commit_hashing mode.
+ *   te_stream_read_submit: validate one window (every object, as the batch calls do) and enqueue
+ *     it in verified form (h_leaves == NULL: unverified, h_status may then be NULL too); returns
+ *     its ticket (1, 2, ... in submission order) without waiting for the device.  A window that
+ *     fails validation gets no ticket.  objs, h_meta and h_leaves are copied; h_slices, h_out,
+ *     h_rejected_mask and h_status must stay valid until the ticket has been waited for.  A
+ *     handle's windows are pipelined as the batch call's are.
+ *   te_stream_read_wait: complete every window up to `ticket`, in submission order; returns the
+ *     first failure among them (TE_OK if none).  A window's h_out, h_status and h_rejected_mask are
+ *     final once its ticket has been waited for.
+ *   te_stream_reader_free: waits for every window, then frees the reader. */
+typedef struct te_stream_reader te_stream_reader;
+int te_stream_reader_new(te_clay *const *coders, size_t ncoders, const te_slicer_cfg *cfg, te_stream_reader **out);
+int te_stream_read_submit(te_stream_reader *r, const uint8_t *h_slices, const te_decode_object *objs,
+                          const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *h_out,
+                          uint32_t *h_rejected_mask, int *h_status, uint64_t *ticket);
+int te_stream_read_wait(te_stream_reader *r, uint64_t ticket);
+void te_stream_reader_free(te_stream_reader *r);
+/* The handle's last te_decode_batch_host / te_decode_verified_batch_host call (zeroed when the call
+ * has passed its argument checks), or the windows of the stream reader on the handle (zeroed by
+ * te_stream_reader_new, summed over its windows as they are enqueued).  Diagnostics; all zero
+ * before the first such call. */
+typedef struct te_read_launch_stats {
+    uint64_t windows;               /* pipeline windows */
+    uint64_t objects;               /* objects of those windows */
+    uint64_t slices_uploaded;       /* slices copied to the device */
+    uint64_t bytes_h2d;             /* their bytes (descriptors and leaves not counted) */
+    uint64_t bytes_d2h;             /* object bytes copied back: the blob_len of every decoded object */
+    uint64_t slices_hashed_host;    /* leaf hashes by the host pool */
+    uint64_t slices_hashed_device;  /* leaf hashes by the leaf-verify kernel */
+    uint64_t host_waits;            /* times the host waited for the device inside the pipeline: one
+                                       per device-hashed window; the final wait for the last windows'
+                                       copies is not counted */
+} te_read_launch_stats;
+int te_clay_read_launch_stats(te_clay *c, te_read_launch_stats *out);
+
+/* ------------------------------------------------------------------------------------------
  * OuterCoder (lib/slicer/src/outer.rs:19-197): single-level Reed-Solomon over
  * GF(2^16) in the Leopard construction of reed-solomon-simd 3.1.0 (parity unpinned: the crate
  * is not in the container).  n chunks, any k reconstruct; chunks 0..k-1 are the

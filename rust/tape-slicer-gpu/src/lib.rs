@@ -259,6 +259,15 @@ impl ClayCoder {
         if s != 0 { fatal(s) }
         unsafe { st.assume_init() }
     }
+    /// The last host read call on this coder, or the stream reader's windows on it (windows,
+    /// objects, slices and bytes uploaded, bytes copied back, where the leaves were hashed, host
+    /// waits).
+    pub fn read_launch_stats(&self) -> ffi::te_read_launch_stats {
+        let mut st = std::mem::MaybeUninit::<ffi::te_read_launch_stats>::zeroed();
+        let s = unsafe { ffi::te_clay_read_launch_stats(self.raw.as_ptr(), st.as_mut_ptr()) };
+        if s != 0 { fatal(s) }
+        unsafe { st.assume_init() }
+    }
 }
 
 impl ErasureCoder for ClayCoder {

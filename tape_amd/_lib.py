@@ -119,6 +119,11 @@ class te_repair_launch_stats(C.Structure):
                [(f, C.c_uint64) for f in ("fold_stripes", "stage_stripes", "generic_stripes")]
 
 
+class te_read_launch_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("windows", "objects", "slices_uploaded", "bytes_h2d", "bytes_d2h",
+                                          "slices_hashed_host", "slices_hashed_device", "host_waits")]
+
+
 class te_outer_launch_stats(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("matrix_launches", "matrix_ptr_launches", "transform_launches",
                                           "low_reg_launches", "decode_launches", "matrix_g", "matrix_kb",
@@ -247,6 +252,16 @@ def _load() -> C.CDLL:
                                                  u8p, sz, vp, u32p, u32p, C.POINTER(i), vp]),
         "te_repair_verified_batch_device": (i, [vp, vp, C.POINTER(te_repair_object), u8p, sz, vp, u32p, vp]),
         "te_slicer_decode_verified": (i, [vp, C.POINTER(te_slicer_cfg), pp, sz, u8p, u8p, sz, szp, u32p]),
+        "te_decode_window_plan": (i, [vp, C.POINTER(te_decode_object), u8p, sz, sz, szp, sz, szp]),
+        "te_decode_batch_host": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_decode_object), u8p, sz, vp, sz]),
+        "te_decode_verified_batch_host": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_decode_object), u8p, u8p,
+                                              sz, vp, u32p, C.POINTER(i), sz]),
+        "te_stream_reader_new": (i, [C.POINTER(vp), sz, C.POINTER(te_slicer_cfg), C.POINTER(vp)]),
+        "te_stream_read_submit": (i, [vp, vp, C.POINTER(te_decode_object), u8p, u8p, sz, vp, u32p, C.POINTER(i),
+                                      C.POINTER(u64)]),
+        "te_stream_read_wait": (i, [vp, u64]),
+        "te_stream_reader_free": (None, [vp]),
+        "te_clay_read_launch_stats": (i, [vp, C.POINTER(te_read_launch_stats)]),
         "te_outer_chunk_bytes": (sz, [u32, sz]),
         "te_outer_encode": (i, [u32, u32, u8p, sz, u8p, sz, szp]),
         "te_outer_decode": (i, [u32, u32, pp, sz, u8p, sz]),

@@ -198,6 +198,109 @@ def decode_batch(slicer: Slicer, slices, objs, metas: bytes, out, stream=None) -
     _check(r, "decode")
 
 
+def _meta_bytes(metas: bytes):
+    return (C.c_uint8 * max(1, len(metas))).from_buffer_copy(metas if metas else b"\0")
+
+
+def decode_window_plan(coder: ClayCoder, objs, metas: bytes, window_bytes: int = 0) -> list[int]:
+    """te_decode_window_plan: the cuts of the host read pipeline's windows (window w = objects
+    [cuts[w], cuts[w+1])); host only."""
+    arr = objs if _is_desc(objs) else decode_descs(objs)
+    nw = C.c_size_t()
+    mb = _meta_bytes(metas)
+    _check(lib.te_decode_window_plan(coder.handle, arr, mb, len(arr), window_bytes, None, 0, C.byref(nw)), "decode")
+    cuts = (C.c_size_t * (nw.value + 1))()
+    _check(lib.te_decode_window_plan(coder.handle, arr, mb, len(arr), window_bytes, cuts, nw.value + 1, C.byref(nw)),
+           "decode")
+    return [int(x) for x in cuts[:nw.value + 1]] if len(arr) else []
+
+
+def decode_host(slicer: Slicer, slices, objs, metas: bytes, out, window_bytes: int = 0) -> None:
+    """te_decode_batch_host: host -> host batched decode.  slices/out are host buffers (numpy arrays
+    or CPU tensors, pinned for full PCIe rate: host_empty); objs / metas as for decode_batch, offsets
+    into slices/out.  Only the slices named in each avail_mask are read.  Synchronous."""
+    arr = objs if _is_desc(objs) else decode_descs(objs)
+    cfg = slicer._cfg()
+    r = lib.te_decode_batch_host(slicer.coder.handle, C.byref(cfg), C.c_void_p(_host_ptr(slices)), arr,
+                                 _meta_bytes(metas), len(arr), C.c_void_p(_host_ptr(out)), window_bytes)
+    _check(r, "decode")
+
+
+def decode_verified_host(slicer: Slicer, slices, objs, metas: bytes, leaves, out, window_bytes: int = 0):
+    """te_decode_verified_batch_host: the gateway's object read (decode.rs:121-139) host -> host,
+    pipelined in windows.  Arguments as decode_host plus each object's n leaf hashes; returns
+    (status, rejected) per object as decode_verified_batch does.  Who hashes follows
+    set_commit_hashing.  Synchronous."""
+    arr = objs if _is_desc(objs) else decode_descs(objs)
+    cfg = slicer._cfg()
+    nobj = len(arr)
+    lb = _leaf_bytes(leaves, nobj, slicer.coder.n())
+    rej = (C.c_uint32 * max(1, nobj))()
+    st = (C.c_int * max(1, nobj))()
+    r = lib.te_decode_verified_batch_host(slicer.coder.handle, C.byref(cfg), C.c_void_p(_host_ptr(slices)), arr,
+                                          _meta_bytes(metas), lb, nobj, C.c_void_p(_host_ptr(out)), rej, st,
+                                          window_bytes)
+    _check(r, "decode")
+    return [int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]]
+
+
+def read_launch_stats(coder: ClayCoder) -> dict:
+    """te_clay_read_launch_stats: windows, objects, uploads, bytes, hashing and host waits of the
+    handle's last host read call (or of the stream reader's windows on it)."""
+    st = _lib.te_read_launch_stats()
+    _check(lib.te_clay_read_launch_stats(coder.handle, C.byref(st)), "decode")
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+
+class StreamReader:
+    """te_stream_reader: ordered, asynchronous reads, the counterpart of StreamWriter.  submit()
+    enqueues a window (verified against `leaves` if given) and returns its ticket at once; wait()
+    completes every window up to a ticket in submission order and returns {ticket: (status,
+    rejected)} for the windows it completed.  The window's host buffers are kept referenced here
+    until its ticket has been waited for."""
+
+    def __init__(self, slicers: list[Slicer]):
+        self._h = None
+        self._cfg = slicers[0]._cfg()
+        self._coders = [s.coder for s in slicers]  # the handles outlive the reader
+        hs = (C.c_void_p * len(slicers))(*[s.coder.handle.value for s in slicers])
+        h = C.c_void_p()
+        _check(lib.te_stream_reader_new(hs, len(slicers), C.byref(self._cfg), C.byref(h)), "decode")
+        self._h = h
+        self._keep = {}
+
+    def submit(self, slices, objs, metas: bytes, out, leaves=None) -> int:
+        arr = objs if _is_desc(objs) else decode_descs(objs)
+        nobj = len(arr)
+        lb = _leaf_bytes(leaves, nobj, self._coders[0].n()) if leaves is not None else None
+        rej = (C.c_uint32 * max(1, nobj))()
+        st = (C.c_int * max(1, nobj))()
+        t = C.c_uint64()
+        r = lib.te_stream_read_submit(self._h, C.c_void_p(_host_ptr(slices)), arr, _meta_bytes(metas), lb, nobj,
+                                      C.c_void_p(_host_ptr(out)), rej, st, C.byref(t))
+        _check(r, "decode")
+        self._keep[t.value] = (slices, out, rej, st, nobj)
+        return t.value
+
+    def wait(self, ticket: int) -> dict:
+        r = lib.te_stream_read_wait(self._h, ticket)
+        res = {}
+        for t in sorted(t for t in self._keep if t <= ticket):
+            _, _, rej, st, nobj = self._keep.pop(t)
+            res[t] = ([int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]])
+        _check(r, "decode")
+        return res
+
+    def close(self) -> None:
+        if self._h:
+            lib.te_stream_reader_free(self._h)
+            self._h = None
+            self._keep.clear()
+
+    def __del__(self):
+        self.close()
+
+
 def decode_range_descs(objs: list[tuple[int, int, int, int, int, int]]):
     """Prepared te_decode_range_object array for decode_range_batch (build once, reuse)."""
     return (_lib.te_decode_range_object * len(objs))(

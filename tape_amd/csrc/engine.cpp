@@ -431,6 +431,10 @@ uint64_t get_u64(const uint8_t *p) {
 
 bool valid_stripe(uint64_t s) { return s == kStripeSizes[0] || s == kStripeSizes[1] || s == kStripeSizes[2]; }
 
+// the host read pipeline's per-handle buffers (te_decode_batch_host, below)
+struct ReadPipe;
+void read_pipe_free(ReadPipe *p);
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -541,6 +545,10 @@ struct te_clay {
     // the same for the encode_enqueue / repair_enqueue launches of the last encode / repair call
     te_encode_launch_stats els{};
     te_repair_launch_stats rls{};
+    // te_decode_batch_host / te_decode_verified_batch_host: their window buffers (kept between
+    // calls, as the encode pipeline's are) and the last call's te_read_launch_stats
+    ReadPipe *rpipe = nullptr;
+    te_read_launch_stats rds{};
 };
 
 // Drain and free everything a handle holds on its device (on that device).
@@ -557,6 +565,8 @@ static void release_device_state(te_clay *c) {
     if (c->cls_fork) (void)hipEventDestroy(c->cls_fork), c->cls_fork = nullptr;
     for (hipEvent_t &pe : c->cls_join)
         if (pe) (void)hipEventDestroy(pe), pe = nullptr;
+    read_pipe_free(c->rpipe);
+    c->rpipe = nullptr;
     c->enc.release();
     c->dec.release();
     c->rep.release();
@@ -4678,6 +4688,613 @@ int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_
     return TE_OK;
 }
 
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Host read pipeline (te_decode_batch_host, te_decode_verified_batch_host, te_stream_reader_*):
+// the decode, class, table and leaf-verify kernels behind a host boundary.  A batch is cut into
+// windows (read_cuts); window w runs on slot w mod 3 -- the handle's three streams, as the encode
+// pipeline's -- in two stages:
+//   A  pick who hashes; host hashing: the pool hashes the present slices where they lie and the
+//      survivor sets are final; enqueue the H2D copies of the slices that go up (each to its slot
+//      i * slice_len of the object's device range: the layout the decode kernels read, so no
+//      repacking kernel); device hashing: enqueue the leaves, the verify kernel and the D2H copy
+//      of the masks, and record the slot's event;
+//   B  device hashing: wait for that event -- the window's one host wait -- and pick the survivor
+//      sets from the masks; enqueue the decode of the objects that have k verified slices and the
+//      D2H copies of their blob_len bytes.
+// The driver runs A(w+1) before B(w): B(w)'s wait is spent with the next window's upload queued
+// behind this window's, and the copy engines, the kernels and the host pool overlap across slots.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct ReadPipe {
+    static constexpr int R = te_clay::kPipe;
+    struct Slot {
+        DevBuf in, out;   // the window's slices (n * slice_len per object) and decoded objects
+        DevBuf ver;       // device hashing: expected leaves | digests | good masks
+        HostBuf verh;     // its page-locked host side: expected leaves | good masks
+        hipEvent_t verified = nullptr;  // after the masks' D2H copy
+    } slot[R];
+};
+
+void read_pipe_free(ReadPipe *p) {  // its streams drained, its device current
+    if (!p) return;
+    for (auto &sl : p->slot) {
+        sl.in.release();
+        sl.out.release();
+        sl.ver.release();
+        sl.verh.release();
+        if (sl.verified) (void)hipEventDestroy(sl.verified);
+    }
+    delete p;
+}
+
+// One window: nobj objects of the caller's arrays (already offset to the window's first object).
+struct ReadWin {
+    te_slicer_cfg cfg{};
+    const uint8_t *h_slices = nullptr;
+    uint8_t *h_out = nullptr;
+    const te_decode_object *objs = nullptr;
+    const uint8_t *h_meta = nullptr, *h_leaves = nullptr;  // h_leaves null: unverified
+    size_t nobj = 0;
+    uint32_t *h_rej = nullptr;
+    int *h_status = nullptr;
+    const int *pre = nullptr;  // verified: each object's outcome on its present slices (read_validate)
+    int mode = TE_HASH_AUTO;
+    // measurement option TEC_DEBUG_KNOBS=1 TEC_READ_COPY_ONLY=1 (scripts/read_pipeline_bench.py): the
+    // window's copies with no hashing and no kernels -- the ceiling of the pipeline on a box
+    bool copy_only = false;
+    // stage A -> stage B
+    bool device_hash = false, resolved = false;
+    std::vector<uint64_t> in_base;  // object o's slice 0 in the slot's input buffer
+    std::vector<uint32_t> good;     // verified present slices (unverified: the present slices)
+    std::vector<DecItem> run;       // the objects that decode; out_off = their place in the slot's output
+    std::vector<CopyRun> hout;
+    uint64_t out_sz = 0;
+};
+
+// Every object checked like Slicer::decode on its present slices (nothing is enqueued before this
+// has passed).  Unverified: the first failure is the call's.  Verified: too few slices is that
+// object's outcome (status[i]), anything else the call's.
+int read_validate(const te_clay *c, const te_decode_object *objs, const uint8_t *h_meta, size_t nobj, bool verified,
+                  int *status) {
+    const uint32_t all = slice_bits(c);
+    for (size_t i = 0; i < nobj; i++) {
+        DecItem it{};
+        const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask & all, it);
+        if (r && !(verified && r == TE_ERR_NOT_ENOUGH_SLICES)) return r;
+        if (status) status[i] = r;
+    }
+    return TE_OK;
+}
+
+// te_decode_window_plan: at least one object per window, then as many as fit.
+int read_cuts(const te_clay *c, const te_decode_object *objs, const uint8_t *h_meta, size_t nobj, size_t window_bytes,
+              std::vector<size_t> &cuts) {
+    if (window_bytes == 0) window_bytes = (size_t)128 << 20;
+    const uint32_t all = slice_bits(c);
+    cuts.assign(1, 0);
+    uint64_t sum = 0;
+    for (size_t i = 0; i < nobj; i++) {
+        te_slice_metadata m;
+        if (int r = te_slice_metadata_from_slice(h_meta + i * TE_META_SIZE, TE_META_SIZE, &m)) return r;
+        const uint64_t b = (uint64_t)__builtin_popcount(objs[i].avail_mask & all) * objs[i].slice_len + m.blob_len;
+        if (i > cuts.back() && sum + b > window_bytes) {
+            cuts.push_back(i);
+            sum = 0;
+        }
+        sum += b;
+    }
+    if (nobj) cuts.push_back(nobj);
+    return TE_OK;
+}
+
+hipStream_t read_slot_stream(te_clay *c, int k) { return k < 2 ? c->pipe[k].s : c->stream; }
+
+int read_streams(te_clay *c) {  // handle locked, its device current
+    if (int r = ensure_stream(c)) return r;
+    for (int k = 0; k < 2; k++)
+        if (!c->pipe[k].s) TE_HIP(hipStreamCreateWithFlags(&c->pipe[k].s, hipStreamNonBlocking));
+    return TE_OK;
+}
+
+// hash_leaf of the window's present slices on the host pool, from the caller's buffer:
+// good[o] = the present slices of object o that match their leaf.  Waits for the pool.
+void read_hash_host(const ReadWin &W, uint32_t n, uint32_t all, int device, std::vector<uint32_t> &good,
+                    te_read_launch_stats &st) {
+    struct Item { const uint8_t *p; uint64_t len; uint32_t obj, bit; };
+    std::vector<Item> items;
+    for (size_t o = 0; o < W.nobj; o++)
+        for (uint32_t b = 0; b < n; b++)
+            if (((W.objs[o].avail_mask & all) >> b) & 1u)
+                items.push_back({W.h_slices + W.objs[o].slices_off + (uint64_t)b * W.objs[o].slice_len,
+                                 W.objs[o].slice_len, (uint32_t)o, b});
+    good.assign(W.nobj, 0);
+    if (items.empty()) return;
+    hh::Pool &pool = hh::Pool::get();
+    // interleaved lanes raise one thread's rate, but a window of a few long slices (a 64 MiB
+    // track: 7..20 slices of ~9.6 MB) needs every thread first
+    const int lanes = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.lanes(), items.size() / (size_t)std::max(1, pool.threads())));
+    auto ok = std::make_shared<std::vector<uint8_t>>(items.size(), 0);
+    auto job = std::make_shared<hh::Job>();
+    std::vector<std::function<void()>> tasks;
+    const uint8_t *leaves = W.h_leaves;
+    for (size_t j0 = 0; j0 < items.size();) {
+        size_t j1 = j0 + 1;  // a task's lanes hash messages of one length
+        while (j1 < items.size() && j1 - j0 < (size_t)lanes && items[j1].len == items[j0].len) j1++;
+        std::vector<Item> part(items.begin() + (ptrdiff_t)j0, items.begin() + (ptrdiff_t)j1);
+        tasks.push_back([part, j0, ok, job, leaves, n] {
+            const int L = (int)part.size();
+            uint8_t dig[hh::kMaxLanes][TE_HASH_SIZE];
+            const uint8_t *src[hh::kMaxLanes];
+            uint8_t *dst[hh::kMaxLanes];
+            for (int l = 0; l < L; l++) {
+                src[l] = part[(size_t)l].p;
+                dst[l] = dig[l];
+            }
+            hh::hash_leaves(L, src, part[0].len, dst);
+            for (int l = 0; l < L; l++) {
+                const Item &t = part[(size_t)l];
+                (*ok)[j0 + (size_t)l] = memcmp(dig[l], leaves + ((size_t)t.obj * n + t.bit) * TE_HASH_SIZE, TE_HASH_SIZE) == 0;
+            }
+            job->done();
+        });
+        j0 = j1;
+    }
+    job->add((int64_t)tasks.size());
+    pool.submit_after(nullptr, device, std::move(tasks));
+    (void)job->wait();
+    for (size_t j = 0; j < items.size(); j++)
+        if ((*ok)[j]) good[items[j].obj] |= 1u << items[j].bit;
+    st.slices_hashed_host += items.size();
+}
+
+// The survivor sets are known: masks and statuses out, the objects that decode and their place in
+// the slot's output buffer.
+void read_resolve(const te_clay *c, ReadWin &W) {
+    const uint32_t all = slice_bits(c);
+    W.run.clear();
+    W.hout.clear();
+    W.out_sz = 0;
+    for (size_t o = 0; o < W.nobj; o++) {
+        const uint32_t avail = W.objs[o].avail_mask & all, ok = avail & W.good[o];
+        if (W.h_leaves && W.h_rej) W.h_rej[o] = avail & ~ok;
+        int st = W.pre ? W.pre[o] : TE_OK;
+        DecItem it{};
+        if (!st) st = decode_validate(c, W.h_meta + o * TE_META_SIZE, W.objs[o].slice_len, ok, it);
+        if (W.h_status) W.h_status[o] = st;
+        W.good[o] = st ? 0u : ok;  // the slices the decode reads from
+        if (st) continue;
+        it.in_base = W.in_base[o];
+        it.out_off = W.out_sz;
+        W.run.push_back(it);
+        if (it.blob_len) {
+            if (!W.hout.empty() && W.hout.back().host + W.hout.back().len == W.objs[o].out_off &&
+                W.hout.back().dev + W.hout.back().len == W.out_sz)
+                W.hout.back().len += it.blob_len;
+            else
+                W.hout.push_back({W.objs[o].out_off, W.out_sz, it.blob_len});
+        }
+        W.out_sz += (it.blob_len + 15) & ~15ull;  // device copies 16-byte aligned
+    }
+    W.resolved = true;
+}
+
+// Stage A of a window on slot k (handle locked, its device current).
+int read_stage_a(te_clay *c, ReadPipe &P, int k, ReadWin &W) {
+    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
+    ReadPipe::Slot &sl = P.slot[k];
+    const hipStream_t s = read_slot_stream(c, k);
+    te_read_launch_stats &st = c->rds;
+    st.windows++;
+    st.objects += W.nobj;
+    W.in_base.resize(W.nobj);
+    W.good.assign(W.nobj, 0);
+    uint64_t in_sz = 0, max_slice = 0, slice_bytes = 0, nslices = 0;
+    bool dword = true;
+    for (size_t o = 0; o < W.nobj; o++) {
+        W.in_base[o] = in_sz;
+        in_sz += ((uint64_t)n * W.objs[o].slice_len + 15) & ~15ull;
+        const uint64_t np = (uint64_t)__builtin_popcount(W.objs[o].avail_mask & all);
+        nslices += np;
+        slice_bytes += np * W.objs[o].slice_len;
+        if (np) max_slice = std::max<uint64_t>(max_slice, W.objs[o].slice_len);
+        dword = dword && W.objs[o].slice_len % 4u == 0;
+    }
+    W.device_hash = W.h_leaves && nslices && dword && !host_hash_wins(W.mode, nslices, max_slice, slice_bytes);
+    if (W.copy_only) W.device_hash = false;
+    if (!W.h_leaves || W.copy_only) {
+        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.objs[o].avail_mask & all;
+        read_resolve(c, W);
+    } else if (!W.device_hash) {
+        read_hash_host(W, n, all, c->device, W.good, st);
+        read_resolve(c, W);
+    } else {
+        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.objs[o].avail_mask & all;  // every present slice goes up
+    }
+    TE_HIP(sl.in.ensure(in_sz + 16));
+    uint8_t *const d_in = sl.in.as<uint8_t>();
+    std::vector<CopyRun> hin;
+    std::vector<te_verify_item> vi;
+    for (size_t o = 0; o < W.nobj; o++) {
+        const uint64_t len = W.objs[o].slice_len;
+        for (uint32_t b = 0; b < n; b++) {
+            if (!((W.good[o] >> b) & 1u) || !len) continue;
+            const uint64_t host = W.objs[o].slices_off + (uint64_t)b * len, dev = W.in_base[o] + (uint64_t)b * len;
+            if (!hin.empty() && hin.back().host + hin.back().len == host && hin.back().dev + hin.back().len == dev)
+                hin.back().len += len;
+            else
+                hin.push_back({host, dev, len});
+            st.slices_uploaded++;
+            st.bytes_h2d += len;
+        }
+        if (W.device_hash) verify_push_slices(vi, o, n, W.in_base[o], len, W.good[o]);
+    }
+    if (int r = copy_runs(hin, d_in, W.h_slices, hipMemcpyHostToDevice, s)) return r;
+    if (!W.device_hash) return TE_OK;
+    // verify_wait's launches without its wait, in the slot's own workspace
+    const size_t exp_b = W.nobj * n * TE_HASH_SIZE, dig_b = vi.size() * TE_HASH_SIZE, mask_b = W.nobj * sizeof(uint32_t);
+    TE_HIP(sl.ver.ensure(exp_b + dig_b + mask_b));
+    TE_HIP(sl.verh.ensure(exp_b + mask_b));
+    uint8_t *const d = sl.ver.as<uint8_t>();
+    uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + exp_b + dig_b);
+    memcpy(sl.verh.p, W.h_leaves, exp_b);
+    TE_HIP(hipMemcpyAsync(d, sl.verh.p, exp_b, hipMemcpyHostToDevice, s));
+    TE_HIP(hipMemsetAsync(d_mask, 0, mask_b, s));
+    if (int r = verify_enqueue(c, d_in, vi.data(), vi.size(), d, d + exp_b, nullptr, d_mask, s)) return r;
+    TE_HIP(hipMemcpyAsync(sl.verh.u8() + exp_b, d_mask, mask_b, hipMemcpyDeviceToHost, s));
+    if (!sl.verified) TE_HIP(hipEventCreateWithFlags(&sl.verified, hipEventDisableTiming | hipEventBlockingSync));
+    TE_HIP(hipEventRecord(sl.verified, s));
+    st.slices_hashed_device += vi.size();
+    return TE_OK;
+}
+
+// The one host wait of a device-hashed window (its device current; the handle need not be locked).
+int read_wait_masks(ReadPipe &P, int k, const ReadWin &W) {
+    if (!W.device_hash || W.resolved) return TE_OK;
+    TE_HIP(hipEventSynchronize(P.slot[k].verified));
+    return TE_OK;
+}
+
+// Stage B (handle locked, its device current, read_wait_masks passed).
+int read_stage_b(te_clay *c, ReadPipe &P, int k, ReadWin &W) {
+    ReadPipe::Slot &sl = P.slot[k];
+    const hipStream_t s = read_slot_stream(c, k);
+    te_read_launch_stats &st = c->rds;
+    if (!W.resolved) {
+        const size_t exp_b = W.nobj * (size_t)c->h.n * TE_HASH_SIZE;
+        memcpy(W.good.data(), sl.verh.u8() + exp_b, W.nobj * sizeof(uint32_t));
+        st.host_waits++;
+        read_resolve(c, W);
+    }
+    if (W.run.empty()) return TE_OK;
+    TE_HIP(sl.out.ensure(W.out_sz + 16));
+    if (!W.copy_only)
+        if (int r = decode_enqueue(c, &W.cfg, sl.in.as<uint8_t>(), W.run.data(), W.run.size(), sl.out.as<uint8_t>(), s, false))
+            return r;
+    for (const CopyRun &r : W.hout) st.bytes_d2h += r.len;
+    return copy_runs(W.hout, sl.out.as<uint8_t>(), W.h_out, hipMemcpyDeviceToHost, s);
+}
+
+int read_drain(te_clay *c) {  // its device current
+    int rc = TE_OK;
+    for (int k = 0; k < ReadPipe::R; k++)
+        if (hipStream_t s = read_slot_stream(c, k)) {
+            const int r = sync_sleep(s);
+            if (!rc) rc = r;
+        }
+    return rc;
+}
+
+int decode_host_impl(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_decode_object *objs,
+                     const uint8_t *h_meta, const uint8_t *h_leaves, bool verified, size_t nobj, uint8_t *h_out,
+                     uint32_t *h_rej, int *h_status, size_t window_bytes) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_slices || !h_out) && nobj)) return TE_ERR_INVALID_ARG;
+    if (verified && ((!h_leaves || !h_status) && nobj)) return TE_ERR_INVALID_ARG;
+    if (nobj > 0xffffffffull / (uint32_t)c->h.n) return TE_ERR_INVALID_ARG;
+    std::vector<int> pre(nobj, TE_OK);
+    if (int r = read_validate(c, objs, h_meta, nobj, verified, pre.data())) return r;
+    std::vector<size_t> cuts;
+    if (int r = read_cuts(c, objs, h_meta, nobj, window_bytes, cuts)) return r;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->rds = te_read_launch_stats{};
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    if (int r = read_streams(c)) return r;
+    if (!c->rpipe) c->rpipe = new ReadPipe();
+    ReadPipe &P = *c->rpipe;
+    const size_t nw = cuts.size() - 1;
+    const size_t n = (size_t)c->h.n;
+    const char *co = tec_knob("TEC_READ_COPY_ONLY");  // read per call: a benchmark switches it between legs
+    const bool copy_only = co && co[0] == '1';
+    std::vector<ReadWin> wins(nw);
+    for (size_t w = 0; w < nw; w++) {
+        ReadWin &W = wins[w];
+        const size_t a = cuts[w];
+        W.cfg = *cfg;
+        W.h_slices = h_slices;
+        W.h_out = h_out;
+        W.objs = objs + a;
+        W.h_meta = h_meta + a * TE_META_SIZE;
+        W.h_leaves = verified ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
+        W.nobj = cuts[w + 1] - a;
+        W.h_rej = h_rej ? h_rej + a : nullptr;
+        W.h_status = h_status ? h_status + a : nullptr;
+        W.pre = verified ? pre.data() + a : nullptr;
+        W.mode = g_commit_hashing.load();
+        W.copy_only = copy_only;
+    }
+    // A(w + 1) before B(w): window w's host wait is spent with the next upload already queued
+    int rc = TE_OK;
+    for (size_t w = 0; w <= nw && !rc; w++) {
+        if (w < nw) rc = read_stage_a(c, P, (int)(w % ReadPipe::R), wins[w]);
+        if (w > 0 && !rc) {
+            const int k = (int)((w - 1) % ReadPipe::R);
+            if (!(rc = read_wait_masks(P, k, wins[w - 1]))) rc = read_stage_b(c, P, k, wins[w - 1]);
+        }
+    }
+    const int r2 = read_drain(c);
+    return rc ? rc : r2;
+}
+
+}  // namespace
+
+// Ordered, asynchronous reads: one host thread per handle runs the handle's windows through the
+// same two stages, A of the next window before B of the last, whenever a next window is queued.
+struct te_stream_reader {
+    struct Job {
+        uint64_t ticket = 0;
+        ReadWin W;
+        std::vector<te_decode_object> objs;
+        std::vector<uint8_t> meta, leaves;
+        std::vector<int> pre;
+        int slot = 0, rc = TE_OK;
+        bool done = false;           // its work is enqueued (or it failed)
+        hipEvent_t ev = nullptr;     // after its last D2H copy
+    };
+    struct Dev {
+        te_clay *c = nullptr;
+        int device = 0;
+        ReadPipe *P = nullptr;
+        std::thread th;
+        std::deque<std::shared_ptr<Job>> q;
+        uint64_t nwin = 0;
+    };
+    std::vector<std::unique_ptr<Dev>> devs;
+    te_slicer_cfg cfg{};
+    int hashing = TE_HASH_AUTO;
+    std::mutex mu;       // queues, tickets, done flags
+    std::condition_variable cv_work, cv_done;
+    std::mutex wait_mu;  // te_stream_read_wait calls complete tickets one caller at a time
+    bool quit = false;
+    uint64_t next = 1;
+    std::map<uint64_t, std::shared_ptr<Job>> tickets;  // submitted, not yet waited
+};
+
+namespace {
+
+void reader_worker(te_stream_reader *r, te_stream_reader::Dev *d) {
+    using Job = te_stream_reader::Job;
+    te_clay *c = d->c;
+    std::shared_ptr<Job> staged;  // stage A done, stage B to do
+    auto finish = [&](const std::shared_ptr<Job> &j, int rc) {
+        if (rc) {
+            // only this window fails; work already enqueued for it may still touch its buffers
+            DeviceGuard dg(d->device);
+            (void)read_drain(c);
+        }
+        std::lock_guard<std::mutex> g(r->mu);
+        j->rc = rc;
+        j->done = true;
+        r->cv_done.notify_all();
+    };
+    for (;;) {
+        std::shared_ptr<Job> nxt;
+        {
+            std::unique_lock<std::mutex> g(r->mu);
+            if (!staged) r->cv_work.wait(g, [&] { return r->quit || !d->q.empty(); });
+            if (!d->q.empty()) {
+                nxt = d->q.front();
+                d->q.pop_front();
+            } else if (!staged) {
+                return;
+            }
+        }
+        int rca = TE_OK;
+        if (nxt) {
+            std::lock_guard<std::mutex> lk(c->mu);
+            DeviceGuard dg(d->device);
+            rca = c->device != d->device ? (int)TE_ERR_INVALID_ARG : hip_status(dg.err);  // handle re-bound under the reader
+            if (!rca) rca = read_stage_a(c, *d->P, nxt->slot, nxt->W);
+        }
+        if (staged) {
+            DeviceGuard dg(d->device);
+            int rc = hip_status(dg.err);
+            if (!rc) rc = read_wait_masks(*d->P, staged->slot, staged->W);  // the handle stays free meanwhile
+            if (!rc) {
+                std::lock_guard<std::mutex> lk(c->mu);
+                rc = read_stage_b(c, *d->P, staged->slot, staged->W);
+                if (!rc) rc = hip_status(hipEventCreateWithFlags(&staged->ev, hipEventDisableTiming | hipEventBlockingSync));
+                if (!rc) rc = hip_status(hipEventRecord(staged->ev, read_slot_stream(c, staged->slot)));
+            }
+            finish(staged, rc);
+            staged.reset();
+        }
+        if (nxt) {
+            if (rca) finish(nxt, rca);
+            else staged = nxt;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int te_decode_window_plan(const te_clay *c, const te_decode_object *objs, const uint8_t *h_meta, size_t nobj,
+                          size_t window_bytes, size_t *cuts, size_t cap, size_t *nwindows) {
+    if (!c || !nwindows || ((!objs || !h_meta) && nobj)) return TE_ERR_INVALID_ARG;
+    *nwindows = 0;
+    std::vector<size_t> v;
+    if (int r = read_cuts(c, objs, h_meta, nobj, window_bytes, v)) return r;
+    *nwindows = v.size() - 1;
+    if (!cuts) return TE_OK;
+    if (cap < v.size()) return TE_ERR_BUFFER_TOO_SMALL;
+    memcpy(cuts, v.data(), v.size() * sizeof(size_t));
+    return TE_OK;
+}
+
+int te_decode_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_decode_object *objs,
+                         const uint8_t *h_meta, size_t nobj, uint8_t *h_out, size_t window_bytes) {
+    return decode_host_impl(c, cfg, h_slices, objs, h_meta, nullptr, false, nobj, h_out, nullptr, nullptr, window_bytes);
+}
+
+int te_decode_verified_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices,
+                                  const te_decode_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                  size_t nobj, uint8_t *h_out, uint32_t *h_rejected_mask, int *h_status,
+                                  size_t window_bytes) {
+    return decode_host_impl(c, cfg, h_slices, objs, h_meta, h_leaves, true, nobj, h_out, h_rejected_mask, h_status,
+                            window_bytes);
+}
+
+int te_clay_read_launch_stats(te_clay *c, te_read_launch_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->rds;
+    return TE_OK;
+}
+
+int te_stream_reader_new(te_clay *const *coders, size_t ncoders, const te_slicer_cfg *cfg, te_stream_reader **out) {
+    if (!out) return TE_ERR_INVALID_ARG;
+    *out = nullptr;
+    if (!coders || ncoders == 0 || !cfg) return TE_ERR_INVALID_ARG;
+    for (size_t i = 0; i < ncoders; i++)
+        if (!coders[i]) return TE_ERR_INVALID_ARG;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    auto *r = new (std::nothrow) te_stream_reader();
+    if (!r) return TE_ERR_OUT_OF_MEMORY;
+    r->cfg = *cfg;
+    r->hashing = g_commit_hashing.load();
+    int rc = TE_OK;
+    for (size_t i = 0; i < ncoders && !rc; i++) {
+        auto d = std::make_unique<te_stream_reader::Dev>();
+        d->c = coders[i];
+        d->device = coders[i]->device;
+        d->P = new ReadPipe();
+        {
+            std::lock_guard<std::mutex> lk(d->c->mu);
+            DeviceGuard dg(d->device);
+            if (!(rc = hip_status(dg.err))) rc = read_streams(d->c);
+            d->c->rds = te_read_launch_stats{};
+        }
+        r->devs.push_back(std::move(d));
+    }
+    if (!rc)
+        for (auto &d : r->devs) d->th = std::thread(reader_worker, r, d.get());
+    if (rc) {
+        te_stream_reader_free(r);
+        return rc;
+    }
+    *out = r;
+    return TE_OK;
+}
+
+int te_stream_read_submit(te_stream_reader *r, const uint8_t *h_slices, const te_decode_object *objs,
+                          const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *h_out,
+                          uint32_t *h_rejected_mask, int *h_status, uint64_t *ticket) {
+    if (!r || !ticket) return TE_ERR_INVALID_ARG;
+    *ticket = 0;
+    if ((!objs || !h_meta || !h_slices || !h_out) && nobj) return TE_ERR_INVALID_ARG;
+    if (h_leaves && !h_status && nobj) return TE_ERR_INVALID_ARG;
+    const te_clay *c0 = r->devs[0]->c;
+    const size_t n = (size_t)c0->h.n;
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    auto j = std::make_shared<te_stream_reader::Job>();
+    j->pre.assign(nobj, TE_OK);
+    if (int rc = read_validate(c0, objs, h_meta, nobj, h_leaves != nullptr, j->pre.data())) return rc;
+    if (nobj) {
+        j->objs.assign(objs, objs + nobj);
+        j->meta.assign(h_meta, h_meta + nobj * TE_META_SIZE);
+        if (h_leaves) j->leaves.assign(h_leaves, h_leaves + nobj * n * TE_HASH_SIZE);
+    }
+    ReadWin &W = j->W;
+    W.cfg = r->cfg;
+    W.h_slices = h_slices;
+    W.h_out = h_out;
+    W.objs = j->objs.data();
+    W.h_meta = j->meta.data();
+    W.h_leaves = h_leaves ? j->leaves.data() : nullptr;
+    W.nobj = nobj;
+    W.h_rej = h_rejected_mask;
+    W.h_status = h_status;
+    W.pre = h_leaves ? j->pre.data() : nullptr;
+    W.mode = r->hashing;
+    std::lock_guard<std::mutex> g(r->mu);
+    const uint64_t t = r->next++;
+    te_stream_reader::Dev &d = *r->devs[(size_t)((t - 1) % r->devs.size())];
+    j->ticket = t;
+    j->slot = (int)(d.nwin++ % ReadPipe::R);
+    r->tickets[t] = j;
+    d.q.push_back(j);
+    r->cv_work.notify_all();
+    *ticket = t;
+    return TE_OK;
+}
+
+int te_stream_read_wait(te_stream_reader *r, uint64_t ticket) {
+    if (!r || ticket == 0) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> wg(r->wait_mu);
+    int first = TE_OK;
+    for (;;) {
+        std::shared_ptr<te_stream_reader::Job> j;
+        int dev = 0;
+        {
+            std::unique_lock<std::mutex> g(r->mu);
+            if (ticket >= r->next) return TE_ERR_INVALID_ARG;  // never submitted
+            if (r->tickets.empty() || r->tickets.begin()->first > ticket) return first;
+            j = r->tickets.begin()->second;
+            r->cv_done.wait(g, [&] { return j->done; });
+            r->tickets.erase(r->tickets.begin());
+            dev = r->devs[(size_t)((j->ticket - 1) % r->devs.size())]->device;
+        }
+        int rc = j->rc;
+        if (j->ev) {
+            DeviceGuard dg(dev);
+            const int r2 = hip_status(hipEventSynchronize(j->ev));
+            if (!rc) rc = r2;
+            (void)hipEventDestroy(j->ev);
+            j->ev = nullptr;
+        }
+        if (!first) first = rc;
+    }
+}
+
+void te_stream_reader_free(te_stream_reader *r) {
+    if (!r) return;
+    if (r->next > 1) (void)te_stream_read_wait(r, r->next - 1);
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        r->quit = true;
+    }
+    r->cv_work.notify_all();
+    for (auto &d : r->devs)
+        if (d->th.joinable()) d->th.join();
+    for (auto &d : r->devs) {
+        std::lock_guard<std::mutex> lk(d->c->mu);
+        DeviceGuard dg(d->device);
+        (void)read_drain(d->c);
+        read_pipe_free(d->P);
+        d->P = nullptr;
+    }
+    delete r;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 // ------------------------------------------------------------------------------------------
 // OuterCoder: GF(2^16) Leopard RS (lib/slicer/src/outer.rs:19-197)
