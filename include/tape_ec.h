@@ -780,6 +780,158 @@ typedef struct te_outer_launch_stats {
 } te_outer_launch_stats;
 int te_outer_last_launch_stats(te_outer_launch_stats *out);
 
+/* ------------------------------------------------------------------------------------------
+ * Snapshot codec (lib/snapshot/src/{encode,decode,chunk}.rs, network/protocol/src/snapshot.rs:
+ * 143-275): the one caller of lib/slicer that runs both coders.  The lz4-compressed log is cut
+ * into segments; each segment gets a 4-byte length prefix (pack_segment) and is spread over the n
+ * spool groups by OuterCoder(ceil(n / 3), n); each of the n symbols gets an 8-byte ChunkNumber
+ * header (SnapshotChunkPayload::pack: the segment index, little endian) and is Clay-encoded by
+ * Slicer::clay_default() (rotated, chunk_index 0) and committed (hash_leaf x 20,
+ * root_from_leaf_hashes::<5>).  The engine takes and returns the compressed bytes: SnapshotLog,
+ * lz4, track records, snapshot_chunk_key and signatures stay with the caller.
+ * Chunk t = segment * total_groups + group is the reference's track_number (encode.rs:83) and the
+ * order of every per-chunk output.  The handle `c` supplies the inner coder (Clay(20,7,16) for
+ * the reference's snapshots; n <= 32).
+ * ------------------------------------------------------------------------------------------ */
+#define TE_SNAPSHOT_HEADER_SIZE 8    /* SnapshotChunkPayload::HEADER_SIZE  chunk.rs:37 */
+#define TE_SNAPSHOT_SEGMENT_HEADER 4 /* SEGMENT_HEADER_SIZE                chunk.rs:63 */
+/* snapshot_outer_k (chunk.rs:94-100): ceil(total_groups / 3), 0 for no groups.  Host only. */
+uint32_t te_snapshot_outer_k(uint32_t total_groups);
+/* snapshot_max_segment_bytes (chunk.rs:103-110): k * TE_OUTER_MAX_CHUNK_BYTES - 4.  Host only. */
+uint64_t te_snapshot_max_segment_bytes(uint32_t total_groups);
+typedef struct te_snapshot_segment {
+    uint64_t start, len;       /* the segment is compressed bytes [start, start + len) */
+    uint64_t symbol_bytes;     /* te_outer_chunk_bytes(k, 4 + len): each of its n outer symbols */
+    uint64_t payload_len;      /* 8 + symbol_bytes: the Clay input of each of its n chunks */
+    te_geometry geom;          /* te_slicer_geometry of a blob of payload_len */
+    uint64_t slices_off;       /* its first chunk's slices in the output: chunk (s, g), slice i at
+                                  slices_off + (g * n_inner + i) * geom.slice_len */
+    /* the two BlobEncoding fields encode_chunk derives from the SYMBOL length, not from the
+     * payload the slicer saw (encode.rs:136-146): size, and num_stripes(symbol.len(), stripe_size)
+     * with the slicer's stripe size (geom.stripe_size, picked for the payload) */
+    uint64_t size, stripe_count;
+} te_snapshot_segment;
+typedef struct te_snapshot_plan_info {
+    uint32_t total_groups, outer_k;
+    uint64_t compressed_len, max_segment_bytes;
+    uint64_t segments;         /* max(1, ceil(len / max_segment_bytes))   encode.rs:63 */
+    uint64_t segment_bytes;    /* max(1, ceil(len / segments))            encode.rs:64 */
+    uint64_t chunks;           /* segments * total_groups */
+    uint64_t total_slice_bytes; /* the encode's slice output */
+} te_snapshot_plan_info;
+/* encode_snapshot's cut (encode.rs:62-71).  segs gets plan->segments entries (NULL: the plan
+ * only; fewer than that, `cap`, is TE_ERR_BUFFER_TOO_SMALL with *plan set).  compressed_len == 0
+ * is one segment with an empty range and a 64-byte symbol.  total_groups == 0 is
+ * TE_ERR_INVALID_ARG (NoGroups); a (k, n - k) the GF(2^16) codec does not support is
+ * TE_ERR_UNSUPPORTED, as in te_outer_encode_device.  Host only. */
+int te_snapshot_plan(const te_clay *c, uint64_t compressed_len, uint32_t total_groups, te_snapshot_plan_info *plan,
+                     te_snapshot_segment *segs, size_t cap);
+
+/* Bytes of device scratch te_snapshot_encode_device needs: every chunk's payload (header +
+ * symbol), each symbol 64-byte aligned.  0 if the plan fails.  Host only. */
+size_t te_snapshot_work_bytes(const te_clay *c, uint64_t compressed_len, uint32_t total_groups);
+/* encode_snapshot's compute (encode.rs:62-154) on the device, enqueued on hip_stream; returns
+ * without waiting.  d_compressed: `len` bytes at ANY byte address.  Outputs (DEVICE):
+ *   d_slices       plan.total_slice_bytes, laid out as te_snapshot_segment.slices_off says;
+ *   d_leaf_hashes  chunk t's 20 leaves at (t * n_inner + i) * 32; NULL: no commitments;
+ *   d_roots        chunk t's root (tree height TE_SLICE_TREE_HEIGHT) at t * 32; NULL: leaves only;
+ *   d_work         te_snapshot_work_bytes of scratch, 64-byte aligned (TE_ERR_INVALID_ARG
+ *                  otherwise; work_bytes too small is TE_ERR_BUFFER_TOO_SMALL).
+ * Four steps: one pack launch writes every payload's header and the k data payloads of every
+ * segment (length prefix, segment bytes, zero padding); the outer recovery symbols are computed
+ * straight into their payload slots (one launch per distinct symbol size: only the last segment's
+ * can differ; none for total_groups == 1); one batched Clay encode of all segments * n payloads;
+ * one commit launch per distinct slice length.  Outer shapes only the transform kernels cover
+ * (te_outer_launch_stats) upload their tables per call and wait for the stream once per launch
+ * (counted in host_waits); OuterCoder(17, 50) and every shape with k <= 32 whose matrix image
+ * fits does not. */
+int te_snapshot_encode_device(te_clay *c, const uint8_t *d_compressed, uint64_t len, uint32_t total_groups,
+                              uint8_t *d_slices, uint8_t *d_leaf_hashes, uint8_t *d_roots, uint8_t *d_work,
+                              size_t work_bytes, void *hip_stream);
+/* HOST -> HOST, in windows of whole segments through the slots of te_encode_batch_host's pipeline
+ * (three streams): a window's compressed bytes are uploaded, the device form's four steps run on
+ * it (its payloads in the slot's input buffer; they never visit the host), its slices and
+ * commitments (h_leaf_hashes / h_roots may be NULL as above) are downloaded, and the next window's
+ * upload and kernels overlap that download.  A window is as many segments as keep its slices
+ * within 128 MiB, at least one; a full segment at 50 groups (~590 MiB of slices, ~210 MiB of
+ * payloads) is a window of its own, so the device holds three windows, not the snapshot.  Slot
+ * buffers above 256 MiB are released when the call returns.  te_snapshot_launch_stats sums over
+ * the windows (pack_launches = windows).  Synchronous; on an error it still waits for the copies
+ * it queued.  TE_ERR_BUFFER_TOO_SMALL when cap is below the plan's total_slice_bytes. */
+int te_snapshot_encode_host(te_clay *c, const uint8_t *h_compressed, uint64_t len, uint32_t total_groups,
+                            uint8_t *h_slices, size_t cap, uint8_t *h_leaf_hashes, uint8_t *h_roots);
+
+/* One fetched chunk track of the snapshot reader (snapshot.rs:143-185): its group and its slices
+ * (obj.out_off is ignored).  The segment is learnt from the decoded header only. */
+typedef struct te_snapshot_track {
+    uint32_t group;
+    uint32_t pad_;
+    te_decode_object obj;
+} te_snapshot_track;
+/* Bytes of device scratch te_snapshot_decode_device needs for these tracks (decoded payloads,
+ * headers, the outer decode's packed segments).  Host only. */
+size_t te_snapshot_decode_work_bytes(const te_clay *c, uint32_t total_groups, const te_snapshot_track *tracks,
+                                     const uint8_t *h_meta, size_t ntracks);
+/* The snapshot read (decode.rs:63-165) on the device.  h_meta: one 48-byte suffix per track;
+ * h_leaves: ntracks * n_inner * 32 bytes (each track's BlobEncoding::leaves), or NULL for the
+ * unverified form.  Steps:
+ *   1. every track is Clay-decoded (te_decode_batch_device, or te_decode_verified_batch_device with
+ *      its h_rejected_mask meaning when h_leaves is given).  A track that cannot decode -- fewer
+ *      than k (verified) slices: TE_ERR_NOT_ENOUGH_SLICES; a suffix or layout that does not
+ *      validate: that error; a payload shorter than 8 bytes: TE_ERR_INVALID_LAYOUT
+ *      (ChunkPayloadTooShort) -- gets that status in h_track_status[t] and is skipped, as the
+ *      reader skips a failed track (snapshot.rs:174-176); the outer code absorbs it.
+ *   2. the decoded tracks' 8-byte headers are gathered by one kernel and the call WAITS ONCE on
+ *      hip_stream to read them (the outer decode takes a host pointer table; the verified form
+ *      has waited once before, for its masks).  h_track_segment[t] = the header's chunk number
+ *      (UINT64_MAX for a skipped track); symbols are filed under it, whatever the caller expected
+ *      (snapshot.rs:167-171).  outer_decode_segments' checks (decode.rs:95-127): no decoded track,
+ *      a gap in 0..segment_count, or fewer than outer_k symbols in a segment return
+ *      TE_ERR_NOT_ENOUGH_SLICES with the reference's message (NoChunks / MissingChunk /
+ *      InsufficientGroups { got, need }; the epoch is the caller's) in te_last_error_detail, which
+ *      the call clears once its arguments are checked: a TE_ERR_NOT_ENOUGH_SLICES from step 3
+ *      carries no such text.
+ *      Symbols of unequal length in a segment or a group >= total_groups are
+ *      TE_ERR_INVALID_LAYOUT; a group repeated within a segment keeps its last track.
+ *   3. te_outer_decode_device_batch per run of segments with one symbol size.
+ *   4. one unpack launch checks every length prefix (4 + len <= k * symbol_bytes) and the total
+ *      against out_cap, copies the segment bytes to their byte-aligned places in d_out (nothing
+ *      is written when a check fails) and writes d_result[0] = status (TE_OK,
+ *      TE_ERR_INVALID_LAYOUT or TE_ERR_BUFFER_TOO_SMALL), d_result[1] = the total length.
+ * Steps 3-4 are enqueued and not waited for.  d_work: te_snapshot_decode_work_bytes, 64-byte
+ * aligned.  h_track_status (ntracks ints) and h_track_segment (ntracks) are required,
+ * h_rejected_mask may be NULL.  d_result: two uint64 (DEVICE). */
+int te_snapshot_decode_device(te_clay *c, uint32_t total_groups, const uint8_t *d_slices,
+                              const te_snapshot_track *tracks, const uint8_t *h_meta, const uint8_t *h_leaves,
+                              size_t ntracks, uint8_t *d_out, uint64_t out_cap, uint8_t *d_work, size_t work_bytes,
+                              int *h_track_status, uint32_t *h_rejected_mask, uint64_t *h_track_segment,
+                              uint64_t *d_result, void *hip_stream);
+/* HOST -> HOST: only the slices named in avail_mask are read from h_slices and uploaded; the
+ * device form; d_result and the bytes are read back after the final wait.  *out_len is set on
+ * TE_OK and on TE_ERR_BUFFER_TOO_SMALL (the length needed).  Every fetched track (a slot of n
+ * slices each), the decoded payloads (about n / outer_k x the compressed length) and the output are
+ * on the device at once: the segment of a track is known only after its Clay decode, so the outer
+ * decode cannot start before the last track.  Device buffers above 256 MiB are released when the
+ * call returns.  Synchronous; on an error it still waits for the copies it queued. */
+int te_snapshot_decode_host(te_clay *c, uint32_t total_groups, const uint8_t *h_slices,
+                            const te_snapshot_track *tracks, const uint8_t *h_meta, const uint8_t *h_leaves,
+                            size_t ntracks, uint8_t *h_out, uint64_t cap, uint64_t *out_len, int *h_track_status,
+                            uint32_t *h_rejected_mask, uint64_t *h_track_segment);
+/* The handle's last te_snapshot_* encode or decode call (diagnostics; zeroed when the call has
+ * passed its argument checks; all zero before the first one).  te_clay_encode_launch_stats /
+ * te_clay_decode_launch_stats report the Clay kernels of the same call. */
+typedef struct te_snapshot_stats {
+    uint64_t segments, chunks;   /* encode: the plan's; decode: segments found, tracks decoded */
+    uint64_t clay_objects;       /* payloads handed to the Clay encode / decode */
+    uint32_t pack_launches, unpack_launches, header_launches;
+    uint32_t outer_launches;     /* rs16 kernel launches (te_outer_launch_stats, summed) */
+    uint32_t commit_launches;
+    uint32_t host_waits;         /* times the call waited for the device before it returned: 0 for
+                                    an encode, 1 for a decode (2 verified); the host forms' final
+                                    wait is not counted */
+} te_snapshot_stats;
+int te_snapshot_launch_stats(te_clay *c, te_snapshot_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ use std::ptr::NonNull;
 use tapeec_sys as ffi;
 
 pub mod slicer_hook;
+pub mod snapshot;
 pub mod stream;
 
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]

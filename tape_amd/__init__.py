@@ -14,3 +14,5 @@ from .slicer import (  # noqa: F401
     DEFAULT_STRIPE_SIZE, GROUP_SIZE, ROTATION_STEP, SLICE_TREE_HEIGHT, STRIPE_SIZES, extract_repair_data,
     repair_request, serve_repair_request, num_stripes, pick_stripe_size, shard_to_slice, slice_to_shard,
 )
+from . import snapshot  # noqa: F401,E402
+from .snapshot import SnapshotChunk, SnapshotError, snapshot_max_segment_bytes, snapshot_outer_k  # noqa: F401,E402

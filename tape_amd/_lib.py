@@ -134,6 +134,27 @@ class te_outer_launch_stats(C.Structure):
                                           "decode_segments")]
 
 
+class te_snapshot_segment(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("start", "len", "symbol_bytes", "payload_len")] + \
+               [("geom", te_geometry)] + [(f, C.c_uint64) for f in ("slices_off", "size", "stripe_count")]
+
+
+class te_snapshot_plan_info(C.Structure):
+    _fields_ = [("total_groups", C.c_uint32), ("outer_k", C.c_uint32)] + \
+               [(f, C.c_uint64) for f in ("compressed_len", "max_segment_bytes", "segments", "segment_bytes", "chunks",
+                                          "total_slice_bytes")]
+
+
+class te_snapshot_track(C.Structure):
+    _fields_ = [("group", C.c_uint32), ("pad_", C.c_uint32), ("obj", te_decode_object)]
+
+
+class te_snapshot_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("segments", "chunks", "clay_objects")] + \
+               [(f, C.c_uint32) for f in ("pack_launches", "unpack_launches", "header_launches", "outer_launches",
+                                          "commit_launches", "host_waits")]
+
+
 def build(verbose: bool = False) -> str:
     """Compile libtapeec.so for gfx950 with hipcc (make -C tape_amd)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True,
@@ -269,6 +290,18 @@ def _load() -> C.CDLL:
         "te_outer_decode_device": (i, [u32, u32, pp, u64, vp, vp]),
         "te_outer_decode_device_batch": (i, [u32, u32, pp, u32, u64, vp, u64, vp]),
         "te_outer_last_launch_stats": (i, [C.POINTER(te_outer_launch_stats)]),
+        "te_snapshot_outer_k": (u32, [u32]),
+        "te_snapshot_max_segment_bytes": (u64, [u32]),
+        "te_snapshot_plan": (i, [vp, u64, u32, C.POINTER(te_snapshot_plan_info), C.POINTER(te_snapshot_segment), sz]),
+        "te_snapshot_work_bytes": (sz, [vp, u64, u32]),
+        "te_snapshot_encode_device": (i, [vp, vp, u64, u32, vp, vp, vp, vp, sz, vp]),
+        "te_snapshot_encode_host": (i, [vp, vp, u64, u32, vp, sz, vp, vp]),
+        "te_snapshot_decode_work_bytes": (sz, [vp, u32, C.POINTER(te_snapshot_track), u8p, sz]),
+        "te_snapshot_decode_device": (i, [vp, u32, vp, C.POINTER(te_snapshot_track), u8p, u8p, sz, vp, u64, vp, sz,
+                                          C.POINTER(i), u32p, C.POINTER(u64), vp, vp]),
+        "te_snapshot_decode_host": (i, [vp, u32, vp, C.POINTER(te_snapshot_track), u8p, u8p, sz, vp, u64,
+                                        C.POINTER(u64), C.POINTER(i), u32p, C.POINTER(u64)]),
+        "te_snapshot_launch_stats": (i, [vp, C.POINTER(te_snapshot_stats)]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)

@@ -549,6 +549,13 @@ struct te_clay {
     // calls, as the encode pipeline's are) and the last call's te_read_launch_stats
     ReadPipe *rpipe = nullptr;
     te_read_launch_stats rds{};
+    // te_snapshot_*: the decode's descriptor arena (payload offsets, segment capacities), its
+    // page-locked header read-back, the host forms' device buffers (kept between calls) and the last
+    // call's te_snapshot_stats
+    Arena snap;
+    HostBuf snap_host;
+    DevBuf snap_in, snap_work, snap_out, snap_commit;
+    te_snapshot_stats sns{};
 };
 
 // Drain and free everything a handle holds on its device (on that device).
@@ -580,6 +587,9 @@ static void release_device_state(te_clay *c) {
     c->hio_out.release();
     c->rec_blob.release();
     c->rec_slices.release();
+    c->snap.release();
+    c->snap_host.release();
+    for (DevBuf *b : {&c->snap_in, &c->snap_work, &c->snap_out, &c->snap_commit}) b->release();
     for (DevBuf *b : {&c->dstore.pats, &c->dstore.hdrs, &c->dstore.steps, &c->dstore.soff}) b->release();
     c->dstore.slot.clear();
     c->dstore.n = 0;
@@ -4488,16 +4498,14 @@ int te_verify_leaves_device(te_clay *c, const uint8_t *d_data, const te_verify_i
     return verify_enqueue(c, d_data, items, nitems, d_expected, d_digests, d_ok, d_good_mask, (hipStream_t)stream);
 }
 
-int te_decode_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
-                                    const te_decode_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
-                                    size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, int *h_status,
-                                    void *stream) {
-    if (!c || !cfg || ((!objs || !h_meta || !h_leaves || !h_status) && nobj)) return TE_ERR_INVALID_ARG;
+}  // extern "C"
+namespace {
+// te_decode_verified_batch_device's work after its argument checks: handle locked, its device
+// current (te_snapshot_decode_device runs it under its own lock).
+int decode_verified_locked(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_decode_object *objs,
+                           const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *d_out,
+                           uint32_t *h_rejected_mask, int *h_status, hipStream_t s) {
     const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
-    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
-    for (size_t i = 0; i < nobj; i++)
-        if (objs[i].slice_len % 4u || objs[i].slices_off % 4u) return TE_ERR_INVALID_ARG;
-    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
     std::vector<DecItem> items(nobj);
     std::vector<te_verify_item> vi;
     for (size_t i = 0; i < nobj; i++) {
@@ -4507,10 +4515,6 @@ int te_decode_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const 
         h_status[i] = r;
         verify_push_slices(vi, i, n, objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask & all);
     }
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->device);
-    TE_HIP(dg.err);
-    hipStream_t s = (hipStream_t)stream;
     std::vector<uint32_t> good(nobj);
     int r = verify_wait(c, d_slices, vi, h_leaves, nobj * n, nobj, good.data(), s);
     if (r) return r;
@@ -4528,6 +4532,24 @@ int te_decode_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const 
     c->dls = te_decode_launch_stats{};
     if (run.empty()) return TE_OK;
     return decode_enqueue(c, cfg, d_slices, run.data(), run.size(), d_out, s, false);
+}
+}  // namespace
+extern "C" {
+
+int te_decode_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                    const te_decode_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                    size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, int *h_status,
+                                    void *stream) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_leaves || !h_status) && nobj)) return TE_ERR_INVALID_ARG;
+    if (nobj > 0xffffffffull / (uint32_t)c->h.n) return TE_ERR_INVALID_ARG;
+    for (size_t i = 0; i < nobj; i++)
+        if (objs[i].slice_len % 4u || objs[i].slices_off % 4u) return TE_ERR_INVALID_ARG;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    return decode_verified_locked(c, cfg, d_slices, objs, h_meta, h_leaves, nobj, d_out, h_rejected_mask, h_status,
+                                  (hipStream_t)stream);
 }
 
 int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
@@ -5308,8 +5330,10 @@ size_t te_outer_chunk_bytes(uint32_t k, size_t len) {  // outer.rs:74-80
 
 }  // extern "C"
 namespace {
-int outer_encode_matrix(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint32_t segments,
-                        uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, hipStream_t s);
+// shard j of a segment at + j * stride (te_outer_encode_device: stride = chunk_bytes; the snapshot
+// encode: its payload slots); wait = false leaves the launch enqueued
+int outer_encode_matrix(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint64_t stride,
+                        uint32_t segments, uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, hipStream_t s, bool wait);
 // te_outer_launch_stats: the outermost te_outer_* call on this thread zeroes the stats once its
 // arguments are checked (te_outer_encode calls te_outer_encode_device); the launchers
 // (rs16.hip) and outer_lut add to them
@@ -5320,11 +5344,15 @@ struct OuterCall {
     OuterCall(const OuterCall &) = delete;
     OuterCall &operator=(const OuterCall &) = delete;
 };
-}
-extern "C" {
-
-int te_outer_encode_device(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint32_t segments,
-                           uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, void *stream) {
+// te_outer_encode_device with the shards of a segment `stride` bytes apart, in and out (the kernels
+// address 16-bit units through in_stride / out_stride; nothing in them assumes stride ==
+// chunk_bytes).  *waited (or NULL): whether the call waited for the stream -- always with
+// wait = true; with wait = false only the transform path does, whose host tables must outlive
+// their copy.
+int outer_encode_strided(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint64_t stride,
+                         uint32_t segments, uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, void *stream, bool wait,
+                         bool *waited) {
+    if (waited) *waited = true;
     if (k == 0 || m == 0 || !d_in || !d_out || chunk_bytes == 0 || chunk_bytes % 64 || chunk_bytes / 2 > 0xffffffffull)
         return TE_ERR_INVALID_ARG;
     if (rs16::use_high_rate(k, m) < 0) return TE_ERR_UNSUPPORTED;
@@ -5333,7 +5361,11 @@ int te_outer_encode_device(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t
     // the encode as a matrix product (rs16_matrix_kernel) when its lookup image fits the LDS budget:
     // OuterCoder(17, 50) 17 x 33; the transforms below otherwise
     if (rs16_mat_supported(k, m) && !tec_knob("TEC_RS16_NO_MATRIX"))
-        return outer_encode_matrix(k, m, d_in, chunk_bytes, segments, seg_in, d_out, seg_out, (hipStream_t)stream);
+    {
+        if (waited) *waited = wait;
+        return outer_encode_matrix(k, m, d_in, chunk_bytes, stride, segments, seg_in, d_out, seg_out, (hipStream_t)stream,
+                                   wait);
+    }
     const rs16::Tables &T = rs16::tables();
     const uint32_t c = rs16::chunk(k, m), span = rs16::skew_span(k, m), wl = rs16::work_len(k, m);
     if ((size_t)span * 128 + (size_t)wl * 256 > 160 * 1024 || span > rs16::kModulus) return TE_ERR_UNSUPPORTED;
@@ -5353,7 +5385,7 @@ int te_outer_encode_device(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t
         Rs16EncArgs a{};
         a.in = d_in;
         a.out = d_out;
-        a.in_stride = a.out_stride = chunk_bytes;
+        a.in_stride = a.out_stride = stride;
         a.seg_in = seg_in;
         a.seg_out = seg_out;
         a.lut = d_lut;
@@ -5367,6 +5399,14 @@ int te_outer_encode_device(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t
     const int r2 = hip_status(hipFreeAsync(d_lut, s));
     if (r == TE_OK) r = hip_status(hipStreamSynchronize(s));  // the host table must outlive the copy
     return r ? r : r2;
+}
+}  // namespace
+extern "C" {
+
+int te_outer_encode_device(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint32_t segments,
+                           uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, void *stream) {
+    return outer_encode_strided(k, m, d_in, chunk_bytes, chunk_bytes, segments, seg_in, d_out, seg_out, stream, true,
+                                nullptr);
 }
 
 int te_outer_encode(uint32_t k, uint32_t n, const uint8_t *data, size_t len, uint8_t *out, size_t cap,
@@ -5476,8 +5516,8 @@ int outer_lut(uint32_t k, uint32_t m, const std::vector<uint32_t> &recv, const s
 
 // The encode matrix's image, cached like a decode pattern's (key: received = none, missing = the
 // marker 0xfffffffe); the launch waits for its stream (te_outer_encode_device's contract).
-int outer_encode_matrix(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint32_t segments,
-                        uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, hipStream_t s) {
+int outer_encode_matrix(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t chunk_bytes, uint64_t stride,
+                        uint32_t segments, uint64_t seg_in, uint8_t *d_out, uint64_t seg_out, hipStream_t s, bool wait) {
     int dev = 0;
     TE_HIP(hipGetDevice(&dev));
     int r = TE_OK;
@@ -5488,7 +5528,7 @@ int outer_encode_matrix(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t ch
         Rs16MatArgs a{};
         a.in = d_in;
         a.out = d_out;
-        a.in_stride = a.out_stride = chunk_bytes;
+        a.in_stride = a.out_stride = stride;
         a.seg_in = seg_in;
         a.seg_out = seg_out;
         a.tab = L->d;
@@ -5498,7 +5538,7 @@ int outer_encode_matrix(uint32_t k, uint32_t m, const uint8_t *d_in, uint64_t ch
         kt.stop();
         if (r == TE_OK) r = hip_status(L->readers.record(s));
     }
-    if (r == TE_OK) r = hip_status(hipStreamSynchronize(s));
+    if (r == TE_OK && wait) r = hip_status(hipStreamSynchronize(s));
     return r;
 }
 
@@ -5662,6 +5702,581 @@ int te_outer_decode_device(uint32_t k, uint32_t n, const uint8_t *const *d_chunk
 int te_outer_decode_device_batch(uint32_t k, uint32_t n, const uint8_t *const *d_chunks, uint32_t segments,
                                  uint64_t chunk_bytes, uint8_t *d_out, uint64_t seg_out, void *stream) {
     return outer_decode_segs(k, n, d_chunks, segments, chunk_bytes, d_out, seg_out, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Snapshot codec (snapshot.hip; lib/snapshot/src/{encode,decode,chunk}.rs,
+// network/protocol/src/snapshot.rs:143-275): OuterCoder and per-group Clay as one device pipeline
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct SnapPlan {
+    te_snapshot_plan_info info{};
+    std::vector<te_snapshot_segment> segs;
+};
+
+// encode_snapshot's cut (encode.rs:62-71) and every segment's geometry
+int snap_plan(const te_clay *c, uint64_t len, uint32_t n, SnapPlan &P) {
+    if (!c || n == 0) return TE_ERR_INVALID_ARG;  // NoGroups
+    const uint32_t k = te_snapshot_outer_k(n);
+    if (n > k && rs16::use_high_rate(k, n - k) < 0) return TE_ERR_UNSUPPORTED;
+    const uint64_t max_seg = te_snapshot_max_segment_bytes(n);
+    te_snapshot_plan_info &I = P.info;
+    I.total_groups = n;
+    I.outer_k = k;
+    I.compressed_len = len;
+    I.max_segment_bytes = max_seg;
+    I.segments = std::max<uint64_t>(1, (len + max_seg - 1) / max_seg);
+    I.segment_bytes = std::max<uint64_t>(1, (len + I.segments - 1) / I.segments);
+    I.chunks = I.segments * n;
+    P.segs.resize(I.segments);
+    uint64_t off = 0;
+    for (uint64_t s = 0; s < I.segments; s++) {
+        te_snapshot_segment &g = P.segs[s];
+        g.start = std::min(s * I.segment_bytes, len);
+        g.len = std::min(g.start + I.segment_bytes, len) - g.start;
+        g.symbol_bytes = te_outer_chunk_bytes(k, TE_SNAPSHOT_SEGMENT_HEADER + g.len);
+        g.payload_len = TE_SNAPSHOT_HEADER_SIZE + g.symbol_bytes;
+        te_slicer_geometry(c, g.payload_len, &g.geom);
+        g.slices_off = off;
+        g.size = g.symbol_bytes;
+        g.stripe_count = te_num_stripes(g.symbol_bytes, g.geom.stripe_size);
+        off += (uint64_t)n * (uint64_t)c->h.n * g.geom.slice_len;
+    }
+    I.total_slice_bytes = off;
+    return TE_OK;
+}
+
+// the payload scratch of segments [s0, s1) of the encode: SnapPackArgs' slots (kernels.hpp)
+uint64_t snap_work_bytes(const SnapPlan &P, uint64_t s0, uint64_t s1) {
+    const uint64_t n = P.info.total_groups;
+    return 64u + (s1 - s0 - 1u) * n * (P.segs[s0].symbol_bytes + 64u) + n * (P.segs[s1 - 1u].symbol_bytes + 64u);
+}
+uint64_t snap_work_bytes(const SnapPlan &P) { return snap_work_bytes(P, 0, P.info.segments); }
+
+te_slicer_cfg snap_cfg(const te_clay *c) {  // Slicer::clay_default(): rotated, chunk_index 0 (slicer.rs:151-159, 214)
+    te_slicer_cfg cfg{};
+    cfg.rotated = 1;
+    cfg.encoding = TE_ENCODING_CLAY;
+    cfg.params = (uint64_t)c->h.n | (uint64_t)c->h.k << 8 | (uint64_t)c->h.d << 16;
+    cfg.chunk_index = 0;
+    return cfg;
+}
+
+int snap_check_coder(const te_clay *c) {  // 20 leaves in a height-5 tree; dword-hashed slices
+    if (c->h.n > (1 << TE_SLICE_TREE_HEIGHT) || c->h.n > (int)TE_COMMIT_MAX_LEAVES) return TE_ERR_UNSUPPORTED;
+    return TE_OK;
+}
+
+// Handle locked, its device current: the four steps for segments [s0, s1) of the plan, enqueued on
+// s.  d_src is segment s0's first byte, d_slices its first slice, d_leaf / d_roots its first
+// chunk's; d_work holds snap_work_bytes(P, s0, s1).  Only the plan's last segment differs in symbol
+// size, so a range is at most two runs.  Adds to c->sns and c->els (the entry points zero them).
+int snapshot_encode_locked(te_clay *c, const SnapPlan &P, uint64_t s0, uint64_t s1, const uint8_t *d_src,
+                           uint8_t *d_slices, uint8_t *d_leaf, uint8_t *d_roots, uint8_t *d_work, hipStream_t s,
+                           Arena *arena = nullptr) {
+    const te_snapshot_plan_info &I = P.info;
+    const uint32_t n = I.total_groups, k = I.outer_k, ni = (uint32_t)c->h.n;
+    const uint64_t S = s1 - s0, sym_a = P.segs[s0].symbol_bytes, sym_b = P.segs[s1 - 1u].symbol_bytes;
+    const uint64_t seg_slots = (uint64_t)n * (sym_a + 64u), out0 = P.segs[s0].slices_off;
+    if (S == 0 || S > 0xffffffffull / n) return TE_ERR_TOO_MUCH_DATA;
+    c->sns.segments += S;
+    c->sns.chunks += S * n;
+    // 1. headers, data payloads, padding
+    {
+        SnapPackArgs a{};
+        a.src = d_src;
+        a.work = d_work;
+        a.len = P.segs[s1 - 1u].start + P.segs[s1 - 1u].len - P.segs[s0].start;
+        a.seg_bytes = I.segment_bytes;
+        a.sym_a = sym_a;
+        a.sym_b = sym_b;
+        a.seg0 = s0;
+        a.segs = (uint32_t)S;
+        a.k = k;
+        a.n = n;
+        KTimer kt(s);
+        TE_HIP(launch_snap_pack(a, s));
+        kt.stop();
+        c->sns.pack_launches++;
+    }
+    // runs of segments with one symbol size: [0, S - 1) and the last, or all of them
+    struct Run { uint64_t first, count, sym; };
+    std::vector<Run> runs;
+    if (sym_a == sym_b) runs.push_back({0, S, sym_a});
+    else { runs.push_back({0, S - 1, sym_a}); runs.push_back({S - 1, 1, sym_b}); }
+    // 2. recovery symbols straight into their payload slots (8 bytes into the first payload)
+    if (n > k) {
+        const OuterCall call;
+        for (const Run &r : runs) {
+            uint8_t *in = d_work + 64u + r.first * seg_slots;
+            bool waited = false;
+            const int e = outer_encode_strided(k, n - k, in, r.sym, r.sym + 64u, (uint32_t)r.count, seg_slots,
+                                               in + (uint64_t)k * (r.sym + 64u), seg_slots, s, false, &waited);
+            if (e) return e;
+            if (waited) c->sns.host_waits++;
+        }
+        const te_outer_launch_stats &os = rs16_launch_stats();
+        c->sns.outer_launches += os.matrix_launches + os.transform_launches + os.low_reg_launches;
+    }
+    // 3. one Clay encode over every payload
+    {
+        std::vector<te_object> objs((size_t)(S * n));
+        for (uint64_t sg = 0; sg < S; sg++) {
+            const te_snapshot_segment &g = P.segs[s0 + sg];
+            for (uint32_t p = 0; p < n; p++) {
+                te_object &o = objs[(size_t)(sg * n + p)];
+                o.data_off = 56u + sg * seg_slots + (uint64_t)p * (g.symbol_bytes + 64u);
+                o.blob_len = g.payload_len;
+                o.out_off = g.slices_off - out0 + (uint64_t)p * ni * g.geom.slice_len;
+                o.chunk_index = 0;
+            }
+        }
+        const te_slicer_cfg cfg = snap_cfg(c);
+        const int e = encode_enqueue(c, &cfg, d_work, objs.data(), objs.size(), d_slices, s, false, arena);
+        if (e) return e;
+        c->sns.clay_objects += objs.size();
+    }
+    // 4. commitments, per run (one slice length each)
+    if (d_leaf) {
+        for (const Run &r : runs) {
+            const te_snapshot_segment &g = P.segs[(size_t)(s0 + r.first)];
+            const uint64_t t0 = r.first * n;
+            const int e = te_commit_batch_device(d_slices + (g.slices_off - out0), (uint64_t)ni * g.geom.slice_len,
+                                                 g.geom.slice_len, ni, (size_t)(r.count * n), TE_SLICE_TREE_HEIGHT,
+                                                 d_leaf + t0 * ni * TE_HASH_SIZE,
+                                                 d_roots ? d_roots + t0 * TE_HASH_SIZE : nullptr, nullptr, s);
+            if (e) return e;
+            c->sns.commit_launches++;
+        }
+    }
+    return TE_OK;
+}
+
+// The host forms keep their device buffers between calls up to this size each; a larger one (a
+// snapshot of many full segments) is released when the call returns, its streams drained.
+constexpr size_t kSnapKeepBytes = (size_t)256 << 20;
+void snap_trim(std::initializer_list<DevBuf *> bufs) {
+    for (DevBuf *b : bufs)
+        if (b->cap > kSnapKeepBytes) b->release();
+}
+
+// The decode's per-track outcome before any device work, and its scratch layout:
+// [payload slots | headers | 64 bytes | packed segments].  A decoded payload is placed 64-byte
+// aligned, so its symbol starts 8 bytes in: the Clay decode kernels store at the alignment their
+// other callers use, and the rs16 kernels, which read 16-bit units, take the 8-mod-64 pointers.
+struct SnapDecLayout {
+    std::vector<int> status;          // per track
+    std::vector<uint64_t> pay_off;    // per track (status TE_OK)
+    std::vector<uint64_t> pay_len;
+    uint64_t hdr_off = 0, packed_off = 0, packed_stride = 0, max_segs = 0, total = 0;
+};
+int snap_decode_layout(const te_clay *c, uint32_t n, const te_snapshot_track *tracks, const uint8_t *h_meta,
+                       size_t ntracks, SnapDecLayout &L) {
+    const uint32_t k = te_snapshot_outer_k(n);
+    const uint32_t all = slice_bits(c);
+    L.status.assign(ntracks, TE_OK);
+    L.pay_off.assign(ntracks, 0);
+    L.pay_len.assign(ntracks, 0);
+    uint64_t off = 0, sym_max = 64, live = 0;
+    for (size_t t = 0; t < ntracks; t++) {
+        DecItem it{};
+        int r = decode_validate(c, h_meta + t * TE_META_SIZE, tracks[t].obj.slice_len, tracks[t].obj.avail_mask & all, it);
+        if (r == TE_OK && it.blob_len < TE_SNAPSHOT_HEADER_SIZE) r = TE_ERR_INVALID_LAYOUT;  // ChunkPayloadTooShort
+        if ((L.status[t] = r)) continue;
+        L.pay_off[t] = off;
+        L.pay_len[t] = it.blob_len;
+        off += (it.blob_len + 63u) / 64u * 64u + 64u;
+        sym_max = std::max<uint64_t>(sym_max, it.blob_len - TE_SNAPSHOT_HEADER_SIZE);
+        live++;
+    }
+    L.hdr_off = off;
+    off += (8u * (uint64_t)ntracks + 63u) / 64u * 64u;
+    L.packed_off = off + 64u;
+    L.packed_stride = (uint64_t)k * ((sym_max + 63u) / 64u * 64u) + 64u;
+    L.max_segs = std::max<uint64_t>(1, live / k);
+    L.total = L.packed_off + L.max_segs * L.packed_stride + 64u;
+    return TE_OK;
+}
+
+void snap_detail(const char *fmt, uint64_t a = 0, uint64_t b = 0, uint64_t d = 0) {
+    snprintf(g_last_error, sizeof(g_last_error), fmt, (unsigned long long)a, (unsigned long long)b, (unsigned long long)d);
+}
+
+// Handle locked, its device current.
+int snapshot_decode_locked(te_clay *c, uint32_t n, const uint8_t *d_slices, const te_snapshot_track *tracks,
+                           const uint8_t *h_meta, const uint8_t *h_leaves, size_t ntracks, uint8_t *d_out, uint64_t out_cap,
+                           uint8_t *d_work, size_t work_bytes, int *h_status, uint32_t *h_rejected, uint64_t *h_segment,
+                           uint64_t *d_result, hipStream_t s) {
+    const uint32_t k = te_snapshot_outer_k(n), ni = (uint32_t)c->h.n;
+    SnapDecLayout L;
+    snap_decode_layout(c, n, tracks, h_meta, ntracks, L);
+    if (work_bytes < L.total) return TE_ERR_BUFFER_TOO_SMALL;
+    g_last_error[0] = 0;  // callers tell NOT_ENOUGH_SLICES apart by the detail: none left from an earlier call
+    c->sns = te_snapshot_stats{};
+    c->dls = te_decode_launch_stats{};
+    for (size_t t = 0; t < ntracks; t++) {
+        h_status[t] = L.status[t];
+        h_segment[t] = ~0ull;
+        if (h_rejected) h_rejected[t] = 0;
+    }
+    // 1. Clay decode of every track that validates
+    std::vector<size_t> live;
+    for (size_t t = 0; t < ntracks; t++)
+        if (!L.status[t]) live.push_back(t);
+    const te_slicer_cfg cfg = snap_cfg(c);
+    if (!live.empty() && h_leaves) {
+        std::vector<te_decode_object> objs(live.size());
+        std::vector<uint8_t> meta(live.size() * TE_META_SIZE), leaves(live.size() * ni * TE_HASH_SIZE);
+        std::vector<uint32_t> rej(live.size());
+        std::vector<int> st(live.size());
+        for (size_t i = 0; i < live.size(); i++) {
+            const size_t t = live[i];
+            objs[i] = tracks[t].obj;
+            objs[i].out_off = L.pay_off[t];
+            if (objs[i].slice_len % 4u || objs[i].slices_off % 4u) return TE_ERR_INVALID_ARG;
+            memcpy(&meta[i * TE_META_SIZE], h_meta + t * TE_META_SIZE, TE_META_SIZE);
+            memcpy(&leaves[i * ni * TE_HASH_SIZE], h_leaves + t * ni * TE_HASH_SIZE, (size_t)ni * TE_HASH_SIZE);
+        }
+        const int e = decode_verified_locked(c, &cfg, d_slices, objs.data(), meta.data(), leaves.data(), objs.size(), d_work,
+                                             rej.data(), st.data(), s);
+        if (e) return e;
+        c->sns.host_waits++;  // the verified masks
+        std::vector<size_t> kept;
+        for (size_t i = 0; i < live.size(); i++) {
+            const size_t t = live[i];
+            if (h_rejected) h_rejected[t] = rej[i];
+            if ((h_status[t] = st[i]) == TE_OK) kept.push_back(t);
+        }
+        c->sns.clay_objects = live.size();
+        live.swap(kept);
+    } else if (!live.empty()) {
+        std::vector<DecItem> items(live.size());
+        for (size_t i = 0; i < live.size(); i++) {
+            const size_t t = live[i];
+            decode_validate(c, h_meta + t * TE_META_SIZE, tracks[t].obj.slice_len, tracks[t].obj.avail_mask & slice_bits(c),
+                            items[i]);
+            items[i].in_base = tracks[t].obj.slices_off;
+            items[i].out_off = L.pay_off[t];
+        }
+        const int e = decode_enqueue(c, &cfg, d_slices, items.data(), items.size(), d_work, s, false);
+        if (e) return e;
+        c->sns.clay_objects = live.size();
+    }
+    c->sns.chunks = live.size();
+    if (live.empty()) {  // decode.rs:95-97
+        snap_detail("NoChunks: snapshot has no decoded chunks");
+        return TE_ERR_NOT_ENOUGH_SLICES;
+    }
+    // 2. the headers, and the one wait
+    Arena &A = c->snap;
+    {
+        std::vector<uint64_t> offs(live.size());
+        for (size_t i = 0; i < live.size(); i++) offs[i] = L.pay_off[live[i]];
+        A.img.clear();
+        const size_t at = A.put(offs.data(), offs.size() * sizeof(uint64_t));
+        int e = A.upload(s);
+        if (e) return e;
+        uint64_t *d_hdr = reinterpret_cast<uint64_t *>(d_work + L.hdr_off);
+        KTimer kt(s);
+        TE_HIP(launch_snap_headers(d_work, A.at<uint64_t>(at), (uint32_t)live.size(), d_hdr, s));
+        kt.stop();
+        c->sns.header_launches++;
+        if ((e = A.mark_done(s))) return e;
+        TE_HIP(c->snap_host.ensure(live.size() * sizeof(uint64_t)));
+        TE_HIP(hipMemcpyAsync(c->snap_host.p, d_hdr, live.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        if ((e = sync_sleep(s))) return e;
+        c->sns.host_waits++;
+    }
+    // symbols_by_segment (snapshot.rs:159-172), in track order
+    std::map<uint64_t, std::vector<size_t>> by_seg;
+    for (size_t i = 0; i < live.size(); i++) {
+        const uint64_t seg = reinterpret_cast<const uint64_t *>(c->snap_host.p)[i];
+        h_segment[live[i]] = seg;
+        by_seg[seg].push_back(live[i]);
+    }
+    // outer_decode_segments' checks (decode.rs:104-127): 0..segment_count contiguous, >= k symbols each
+    {
+        uint64_t want = 0;
+        for (const auto &kv : by_seg) {
+            if (kv.first != want) break;
+            want++;
+        }
+        if (want != by_seg.size()) {
+            snap_detail("MissingChunk: missing decoded chunk %llu", want);
+            return TE_ERR_NOT_ENOUGH_SLICES;
+        }
+    }
+    for (const auto &kv : by_seg)
+        if (kv.second.size() < k) {
+            snap_detail("InsufficientGroups: only %llu/%llu groups decoded for chunk %llu", kv.second.size(), k, kv.first);
+            return TE_ERR_NOT_ENOUGH_SLICES;
+        }
+    const uint64_t S = by_seg.size();
+    c->sns.segments = S;
+    if (S > L.max_segs || S > 65535u) return TE_ERR_INVALID_LAYOUT;  // cannot happen with >= k tracks each
+    // OuterCoder::decode's own checks (outer.rs:131-170), then its pointer table
+    std::vector<uint64_t> sym(S);
+    std::vector<const uint8_t *> ptr((size_t)S * n, nullptr);
+    for (const auto &kv : by_seg) {
+        const uint64_t cb = L.pay_len[kv.second.front()] - TE_SNAPSHOT_HEADER_SIZE;
+        for (size_t t : kv.second) {
+            if (L.pay_len[t] - TE_SNAPSHOT_HEADER_SIZE != cb || tracks[t].group >= n) return TE_ERR_INVALID_LAYOUT;
+            ptr[(size_t)kv.first * n + tracks[t].group] = d_work + L.pay_off[t] + TE_SNAPSHOT_HEADER_SIZE;  // last wins
+        }
+        if ((uint64_t)k * cb + 64u > L.packed_stride) return TE_ERR_INVALID_LAYOUT;
+        sym[kv.first] = cb;
+    }
+    // 3. outer decode, one call per run of segments with one symbol size
+    uint8_t *d_packed = d_work + L.packed_off;
+    for (uint64_t a = 0; a < S;) {
+        uint64_t b = a + 1;
+        while (b < S && sym[b] == sym[a]) b++;
+        const int e = te_outer_decode_device_batch(k, n, ptr.data() + (size_t)a * n, (uint32_t)(b - a), sym[a],
+                                                   d_packed + a * L.packed_stride, L.packed_stride, s);
+        if (e) return e;
+        const te_outer_launch_stats &os = rs16_launch_stats();
+        c->sns.outer_launches += os.matrix_launches + os.decode_launches;
+        a = b;
+    }
+    // 4. unpack
+    {
+        std::vector<uint64_t> cap(S);
+        for (uint64_t g = 0; g < S; g++) cap[g] = (uint64_t)k * sym[g];
+        A.img.clear();
+        const size_t at = A.put(cap.data(), cap.size() * sizeof(uint64_t));
+        int e = A.upload(s);
+        if (e) return e;
+        SnapUnpackArgs a{};
+        a.packed = d_packed;
+        a.cap = A.at<uint64_t>(at);
+        a.out = d_out;
+        a.result = d_result;
+        a.stride = L.packed_stride;
+        a.out_cap = out_cap;
+        a.segs = (uint32_t)S;
+        KTimer kt(s);
+        TE_HIP(launch_snap_unpack(a, s));
+        kt.stop();
+        c->sns.unpack_launches++;
+        if ((e = A.mark_done(s))) return e;
+    }
+    return TE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t te_snapshot_outer_k(uint32_t total_groups) { return total_groups == 0 ? 0u : (total_groups + 2u) / 3u; }
+
+uint64_t te_snapshot_max_segment_bytes(uint32_t total_groups) {
+    const uint64_t k = te_snapshot_outer_k(total_groups);
+    return k == 0 ? 0u : k * TE_OUTER_MAX_CHUNK_BYTES - TE_SNAPSHOT_SEGMENT_HEADER;
+}
+
+int te_snapshot_plan(const te_clay *c, uint64_t compressed_len, uint32_t total_groups, te_snapshot_plan_info *plan,
+                     te_snapshot_segment *segs, size_t cap) {
+    if (!c || !plan) return TE_ERR_INVALID_ARG;
+    SnapPlan P;
+    const int r = snap_plan(c, compressed_len, total_groups, P);
+    if (r) return r;
+    *plan = P.info;
+    if (!segs) return TE_OK;
+    if (cap < P.segs.size()) return TE_ERR_BUFFER_TOO_SMALL;
+    memcpy(segs, P.segs.data(), P.segs.size() * sizeof(te_snapshot_segment));
+    return TE_OK;
+}
+
+size_t te_snapshot_work_bytes(const te_clay *c, uint64_t compressed_len, uint32_t total_groups) {
+    SnapPlan P;
+    if (snap_plan(c, compressed_len, total_groups, P)) return 0;
+    return (size_t)snap_work_bytes(P);
+}
+
+int te_snapshot_encode_device(te_clay *c, const uint8_t *d_compressed, uint64_t len, uint32_t total_groups,
+                              uint8_t *d_slices, uint8_t *d_leaf_hashes, uint8_t *d_roots, uint8_t *d_work,
+                              size_t work_bytes, void *stream) {
+    if (!c || (!d_compressed && len) || !d_slices || !d_work || (d_roots && !d_leaf_hashes) ||
+        (reinterpret_cast<uintptr_t>(d_work) & 63u))
+        return TE_ERR_INVALID_ARG;
+    SnapPlan P;
+    int r = snap_plan(c, len, total_groups, P);
+    if (r) return r;
+    if ((r = snap_check_coder(c))) return r;
+    if (work_bytes < snap_work_bytes(P)) return TE_ERR_BUFFER_TOO_SMALL;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    c->sns = te_snapshot_stats{};
+    c->els = te_encode_launch_stats{};
+    return snapshot_encode_locked(c, P, 0, P.info.segments, d_compressed, d_slices, d_leaf_hashes, d_roots, d_work,
+                                  (hipStream_t)stream);
+}
+
+int te_snapshot_encode_host(te_clay *c, const uint8_t *h_compressed, uint64_t len, uint32_t total_groups,
+                            uint8_t *h_slices, size_t cap, uint8_t *h_leaf_hashes, uint8_t *h_roots) {
+    if (!c || (!h_compressed && len) || (h_roots && !h_leaf_hashes)) return TE_ERR_INVALID_ARG;
+    SnapPlan P;
+    int r = snap_plan(c, len, total_groups, P);
+    if (r) return r;
+    if ((r = snap_check_coder(c))) return r;
+    if (!h_slices || cap < P.info.total_slice_bytes) return TE_ERR_BUFFER_TOO_SMALL;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    // Windows of whole segments through the encode pipeline's slots (te_encode_batch_host's: three
+    // streams, each slot its own arena and buffers), so window w + 1's upload and kernels overlap
+    // window w's slice download and the device holds three windows, not the snapshot.  A window is
+    // as many segments as keep its slices within 128 MiB, at least one: a full segment at 50 groups
+    // (~590 MiB of slices) is a window of its own.  The payloads live in the slot's input buffer,
+    // behind the window's compressed bytes, and never leave the device.
+    if ((r = ensure_stream(c))) return r;
+    for (int q = 0; q < 2; q++)
+        if (!c->pipe[q].s) TE_HIP(hipStreamCreateWithFlags(&c->pipe[q].s, hipStreamNonBlocking));
+    auto slot_stream = [&](size_t q) { return q < 2 ? c->pipe[q].s : c->stream; };
+    uint64_t window_bytes = (uint64_t)128 << 20;
+    if (const char *e = tec_knob("TEC_SNAPSHOT_WINDOW_BYTES")) {  // tests: force several windows
+        const uint64_t v = strtoull(e, nullptr, 10);
+        if (v) window_bytes = v;
+    }
+    const uint64_t S = P.info.segments, n = total_groups, ni = (uint64_t)c->h.n;
+    c->sns = te_snapshot_stats{};
+    c->els = te_encode_launch_stats{};
+    int rc = TE_OK;
+    size_t w = 0;
+    for (uint64_t s0 = 0; s0 < S && rc == TE_OK; w++) {
+        auto slices_end = [&](uint64_t sg) { return sg < S ? P.segs[sg].slices_off : P.info.total_slice_bytes; };
+        uint64_t s1 = s0 + 1;
+        while (s1 < S && slices_end(s1 + 1) - slices_end(s0) <= window_bytes) s1++;
+        te_clay::Slot &sl = c->pipe[w % te_clay::kPipe];
+        const hipStream_t ss = slot_stream(w % te_clay::kPipe);
+        const uint64_t work_b = (snap_work_bytes(P, s0, s1) + 63u) / 64u * 64u;
+        const uint64_t in_b = P.segs[s1 - 1].start + P.segs[s1 - 1].len - P.segs[s0].start;
+        const uint64_t out_b = slices_end(s1) - slices_end(s0), t0 = s0 * n, nt = (s1 - s0) * n;
+        const uint64_t leaf_b = nt * ni * TE_HASH_SIZE, root_b = nt * TE_HASH_SIZE;
+        if ((rc = hip_status(sl.in.ensure((size_t)(work_b + in_b + 64u)))) || (rc = hip_status(sl.out.ensure((size_t)out_b))) ||
+            (rc = hip_status(sl.commit.ensure((size_t)(leaf_b + root_b + 64u)))))
+            break;
+        uint8_t *d_work = sl.in.as<uint8_t>(), *d_src = d_work + work_b;
+        uint8_t *d_leaf = h_leaf_hashes ? sl.commit.as<uint8_t>() : nullptr;
+        uint8_t *d_root = h_roots ? sl.commit.as<uint8_t>() + leaf_b : nullptr;
+        if (in_b && (rc = hip_status(hipMemcpyAsync(d_src, h_compressed + P.segs[s0].start, (size_t)in_b,
+                                                    hipMemcpyHostToDevice, ss))))
+            break;
+        if ((rc = snapshot_encode_locked(c, P, s0, s1, d_src, sl.out.as<uint8_t>(), d_leaf, d_root, d_work, ss, &sl.arena)))
+            break;
+        if ((rc = hip_status(hipMemcpyAsync(h_slices + slices_end(s0), sl.out.p, (size_t)out_b, hipMemcpyDeviceToHost, ss))))
+            break;
+        if (d_leaf && (rc = hip_status(hipMemcpyAsync(h_leaf_hashes + t0 * ni * TE_HASH_SIZE, d_leaf, (size_t)leaf_b,
+                                                      hipMemcpyDeviceToHost, ss))))
+            break;
+        if (d_root &&
+            (rc = hip_status(hipMemcpyAsync(h_roots + t0 * TE_HASH_SIZE, d_root, (size_t)root_b, hipMemcpyDeviceToHost, ss))))
+            break;
+        s0 = s1;
+    }
+    // also after a failure: copies from and to the caller's buffers may still be queued
+    for (size_t q = 0; q < te_clay::kPipe; q++) {
+        const int r2 = sync_sleep(slot_stream(q));
+        if (rc == TE_OK) rc = r2;
+    }
+    for (auto &sl : c->pipe) snap_trim({&sl.in, &sl.out, &sl.commit});
+    return rc;
+}
+
+size_t te_snapshot_decode_work_bytes(const te_clay *c, uint32_t total_groups, const te_snapshot_track *tracks,
+                                     const uint8_t *h_meta, size_t ntracks) {
+    if (!c || total_groups == 0 || ((!tracks || !h_meta) && ntracks)) return 0;
+    SnapDecLayout L;
+    snap_decode_layout(c, total_groups, tracks, h_meta, ntracks, L);
+    return (size_t)L.total;
+}
+
+int te_snapshot_decode_device(te_clay *c, uint32_t total_groups, const uint8_t *d_slices,
+                              const te_snapshot_track *tracks, const uint8_t *h_meta, const uint8_t *h_leaves,
+                              size_t ntracks, uint8_t *d_out, uint64_t out_cap, uint8_t *d_work, size_t work_bytes,
+                              int *h_track_status, uint32_t *h_rejected_mask, uint64_t *h_track_segment,
+                              uint64_t *d_result, void *stream) {
+    if (!c || total_groups == 0 || !d_work || !d_result || (!d_out && out_cap) ||
+        ((!tracks || !h_meta || !d_slices || !h_track_status || !h_track_segment) && ntracks) ||
+        (reinterpret_cast<uintptr_t>(d_work) & 63u) || ntracks > 0xffffffffull / (uint32_t)c->h.n)
+        return TE_ERR_INVALID_ARG;
+    const uint32_t k = te_snapshot_outer_k(total_groups);
+    if (total_groups > k && rs16::use_high_rate(k, total_groups - k) < 0) return TE_ERR_UNSUPPORTED;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    return snapshot_decode_locked(c, total_groups, d_slices, tracks, h_meta, h_leaves, ntracks, d_out, out_cap, d_work,
+                                  work_bytes, h_track_status, h_rejected_mask, h_track_segment, d_result,
+                                  (hipStream_t)stream);
+}
+
+int te_snapshot_decode_host(te_clay *c, uint32_t total_groups, const uint8_t *h_slices, const te_snapshot_track *tracks,
+                            const uint8_t *h_meta, const uint8_t *h_leaves, size_t ntracks, uint8_t *h_out, uint64_t cap,
+                            uint64_t *out_len, int *h_track_status, uint32_t *h_rejected_mask, uint64_t *h_track_segment) {
+    if (!c || total_groups == 0 || (!h_out && cap) ||
+        ((!tracks || !h_meta || !h_slices || !h_track_status || !h_track_segment) && ntracks) ||
+        ntracks > 0xffffffffull / (uint32_t)c->h.n)
+        return TE_ERR_INVALID_ARG;
+    const uint32_t k = te_snapshot_outer_k(total_groups), ni = (uint32_t)c->h.n, all = slice_bits(c);
+    if (total_groups > k && rs16::use_high_rate(k, total_groups - k) < 0) return TE_ERR_UNSUPPORTED;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    int r = ensure_stream(c);
+    if (r) return r;
+    hipStream_t s = c->stream;
+    // device image of the tracks: a slot of n slices each, only the present ones uploaded
+    std::vector<te_snapshot_track> dt(tracks, tracks + ntracks);
+    uint64_t in_b = 0;
+    for (size_t t = 0; t < ntracks; t++) {
+        dt[t].obj.slices_off = in_b;
+        in_b += ((uint64_t)ni * tracks[t].obj.slice_len + 63u) / 64u * 64u;
+    }
+    SnapDecLayout L;
+    snap_decode_layout(c, total_groups, tracks, h_meta, ntracks, L);
+    TE_HIP(c->snap_in.ensure((size_t)in_b + 64));
+    TE_HIP(c->snap_work.ensure((size_t)L.total));
+    TE_HIP(c->snap_out.ensure((size_t)cap + 64));
+    TE_HIP(c->snap_commit.ensure(64));
+    for (size_t t = 0; t < ntracks && r == TE_OK; t++)
+        for (uint32_t i = 0; i < ni && r == TE_OK; i++)
+            if (((tracks[t].obj.avail_mask & all) >> i) & 1u)
+                r = hip_status(hipMemcpyAsync(
+                    c->snap_in.as<uint8_t>() + dt[t].obj.slices_off + (uint64_t)i * tracks[t].obj.slice_len,
+                    h_slices + tracks[t].obj.slices_off + (uint64_t)i * tracks[t].obj.slice_len,
+                    (size_t)tracks[t].obj.slice_len, hipMemcpyHostToDevice, s));
+    uint64_t *d_res = c->snap_commit.as<uint64_t>();
+    uint64_t res[2] = {0, 0};
+    if (r == TE_OK)
+        r = snapshot_decode_locked(c, total_groups, c->snap_in.as<uint8_t>(), dt.data(), h_meta, h_leaves, ntracks,
+                               c->snap_out.as<uint8_t>(), cap, c->snap_work.as<uint8_t>(), (size_t)L.total, h_track_status,
+                               h_rejected_mask, h_track_segment, d_res, s);
+    if (r == TE_OK) r = hip_status(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, s));
+    // also after a failure: uploads from the caller's slices may still be queued
+    const int r2 = sync_sleep(s);
+    if (r == TE_OK) r = r2;
+    if (r == TE_OK) {
+        if (out_len && (res[0] == TE_OK || res[0] == TE_ERR_BUFFER_TOO_SMALL)) *out_len = res[1];
+        r = (int)res[0];
+    }
+    if (r == TE_OK && res[1]) r = hip_status(hipMemcpy(h_out, c->snap_out.p, (size_t)res[1], hipMemcpyDeviceToHost));
+    snap_trim({&c->snap_in, &c->snap_work, &c->snap_out});
+    return r;
+}
+
+int te_snapshot_launch_stats(te_clay *c, te_snapshot_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->sns;
+    return TE_OK;
 }
 
 }  // extern "C"

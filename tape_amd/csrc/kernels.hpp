@@ -457,4 +457,33 @@ inline uint32_t repair_wgs(uint32_t words_per_stripe, uint32_t g) { return ((wor
 bool encode_rows_supported(int n, int k, int d);
 size_t encode_rows_scratch_bytes(const EncArgs &a);  // a.njobs, a.groups_per_stripe set
 
+// ---- snapshot codec (snapshot.hip; lib/snapshot/src/{encode,decode,chunk}.rs) ----
+// Payload slots of the encode: segment s < segs - 1 has symbols of sym_a bytes, the last one of
+// sym_b; a slot is its symbol + 64 bytes, and slot p of segment s starts at
+// work + 56 + s * n * (sym_a + 64) + p * (sym + 64): the 8-byte header ends on a 64-byte boundary,
+// where the symbol starts.
+struct SnapPackArgs {
+    const uint8_t *src;      // the compressed bytes (any alignment)
+    uint8_t *work;           // 64-byte aligned
+    uint64_t len, seg_bytes; // total compressed bytes; bytes per segment (the last one: the rest)
+    uint64_t sym_a, sym_b;
+    uint64_t seg0;           // the snapshot's index of the first segment here (the headers' chunk number)
+    uint32_t segs, k, n;
+};
+hipError_t launch_snap_pack(const SnapPackArgs &a, hipStream_t s);
+// Header gather of the decode: hdr[i] = the 8 bytes at work + off[i] (8-byte aligned).
+hipError_t launch_snap_headers(const uint8_t *work, const uint64_t *off, uint32_t count, uint64_t *hdr, hipStream_t s);
+// Unpack: segment s's packed bytes (u32 LE length, then the bytes) at packed + s * stride,
+// cap[s] = k * symbol_bytes valid there; 16 bytes before `packed` and after each segment's cap
+// are readable.  result[0] = status (0, 5 invalid layout, 25 buffer too small), result[1] = total.
+struct SnapUnpackArgs {
+    const uint8_t *packed;
+    const uint64_t *cap;
+    uint8_t *out;
+    uint64_t *result;
+    uint64_t stride, out_cap;
+    uint32_t segs;
+};
+hipError_t launch_snap_unpack(const SnapUnpackArgs &a, hipStream_t s);
+
 }  // namespace tec
