@@ -426,6 +426,13 @@ int te_decode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
  *                    straight from the slices, nothing is decoded;
  *   TE_RANGE_DECODE  anything else: the stripe is decoded as in the full call (same pattern) and
  *                    only the window's bytes [lo, hi) of the stripe are stored.
+ * With te_clay_set_range_chunk_path on (off by default) a third class takes stripes out of
+ * TE_RANGE_DECODE:
+ *   TE_RANGE_CHUNK   exactly one of the data chunks the window intersects is an absent slice's:
+ *                    that chunk's piece is rebuilt by a node-recover class kernel (7 chunks read,
+ *                    the window's bytes of 1 written) and the present chunks' pieces are gathered.
+ *                    Clay(20,7,16) only, where a node recover of the stripe would run a class
+ *                    kernel; two or more erased chunks in the window stay TE_RANGE_DECODE.
  * Meaning: Slicer::decode (slicer.rs:298-364) followed by bytes[start..start + len]; start = 0,
  * len = blob_len is byte-identical to the full decode.  start + len > blob_len (or an overflow) is
  * TE_ERR_INVALID_ARG; len == 0 is valid and writes nothing; fewer than k present slices is
@@ -437,6 +444,7 @@ int te_decode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
  * ------------------------------------------------------------------------------------------ */
 #define TE_RANGE_COPY 0
 #define TE_RANGE_DECODE 1
+#define TE_RANGE_CHUNK 2
 /* Host only: the plan of a ranged read of an object of blob_len bytes encoded by this coder
  * (geometry as te_slicer_geometry).  *first_stripe = s0, *nstripes = touched stripes (0 for
  * len == 0); for touched stripe i (stripe s0 + i): classes[i], and the window [lo[i], hi[i]) in
@@ -445,6 +453,24 @@ int te_decode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
 int te_slicer_range_plan(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
                          uint64_t start, uint64_t len, uint64_t *first_stripe, uint64_t *nstripes,
                          uint32_t *classes, uint64_t *lo, uint64_t *hi);
+/* The chunk path of ranged reads (TE_RANGE_CHUNK), per handle, 0 = off (the default) / 1 = on.
+ * Off, every ranged call classifies, launches and counts exactly as without it.  On, a touched
+ * stripe whose window holds exactly one erased data chunk x -- bytes [max(lo, x*cs),
+ * min(hi, (x+1)*cs)) -- becomes one windowed recover job: lost node = shard x, the survivor set
+ * the stripe's full decode would read, kernel class 8 + 2*a0 (a0 = its known column-0 nodes), the
+ * per-call kernels up to 64 stripes in the call (decode stripes included) and the batch kernels
+ * above.  Other profiles, sub-chunks below 8 bytes and objects past the class kernels' 31-bit
+ * offsets keep TE_RANGE_DECODE.  Results are byte-identical either way. */
+int te_clay_set_range_chunk_path(te_clay *c, int on);
+int te_clay_range_chunk_path(const te_clay *c);
+/* te_slicer_range_plan plus the chunk path: with chunk_path != 0, classes[i] is TE_RANGE_CHUNK
+ * exactly where a ranged call with the knob on rebuilds one chunk, and shards[i] is that data
+ * shard (UINT32_MAX for every other stripe).  chunk_path == 0: classes, lo and hi equal
+ * te_slicer_range_plan's and every shards[i] is UINT32_MAX.  shards may be NULL.  The handle's own
+ * knob is not read.  Host only, every profile. */
+int te_slicer_range_plan_ex(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
+                            uint64_t start, uint64_t len, int chunk_path, uint64_t *first_stripe,
+                            uint64_t *nstripes, uint32_t *classes, uint64_t *lo, uint64_t *hi, uint32_t *shards);
 typedef struct te_decode_range_object {  /* te_decode_object plus the window */
     uint64_t slices_off;  /* slice i at d_slices + slices_off + i*slice_len */
     uint64_t slice_len;
@@ -463,14 +489,15 @@ int te_decode_range_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uin
 /* The per-call host form beside te_slicer_decode (the single-track object_response_ranged,
  * routes.rs:90-91): out gets the window's len bytes (cap >= len), *out_len = len.  Only the
  * touched stripes' chunks [s*cs, (s+1)*cs) of the slices each stripe's decode reads are staged to
- * the device (a copy stripe: only the present data-chunk bytes it reads); the metadata suffix is
+ * the device (a copy stripe: only the present data-chunk bytes it reads; a TE_RANGE_CHUNK stripe:
+ * its recover job's k chunks and the window's other present pieces); the metadata suffix is
  * read on the host.  A page-locked `out` is written by the kernels directly.  (GPU) */
 int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
                            uint64_t start, uint64_t len, uint8_t *out, size_t cap, size_t *out_len);
 /* The handle's last ranged call (diagnostics; zeroed when such a call has passed its argument
  * checks; te_clay_decode_launch_stats reports which decode kernels ran for its decode stripes). */
 typedef struct te_range_launch_stats {
-    uint64_t stripes_touched;  /* = stripes_decoded + stripes_copied */
+    uint64_t stripes_touched;  /* = stripes_decoded + stripes_copied (+ te_range_chunk_stats.stripes_rebuilt) */
     uint64_t stripes_decoded;
     uint64_t stripes_copied;
     uint64_t gather_jobs;      /* chunk pieces the one gather launch copied */
@@ -478,6 +505,16 @@ typedef struct te_range_launch_stats {
                                   the device form */
 } te_range_launch_stats;
 int te_clay_range_launch_stats(te_clay *c, te_range_launch_stats *out);
+/* The chunk path's share of the handle's last ranged call (all zero with the knob off).  A rebuilt
+ * stripe counts in te_range_launch_stats.stripes_touched and here, not in stripes_decoded or
+ * stripes_copied; its present pieces count in both gather_jobs; te_clay_decode_launch_stats
+ * reports its launch under class_launches[8 + 2*a0] and its stripe in class_stripes. */
+typedef struct te_range_chunk_stats {
+    uint64_t stripes_rebuilt;  /* TE_RANGE_CHUNK stripes: one windowed recover job each */
+    uint64_t gather_jobs;      /* present chunk pieces of those stripes in the call's gather launch */
+    uint64_t bytes_stored;     /* bytes the windowed recover jobs stored (sum of their windows) */
+} te_range_chunk_stats;
+int te_clay_range_chunk_launch_stats(te_clay *c, te_range_chunk_stats *out);
 
 typedef struct te_repair_object {
     const te_repair_plan *plan;

@@ -150,6 +150,42 @@ impl ClayCoder {
         unsafe { ffi::te_clay_range_launch_stats(self.raw.as_ptr(), &mut st) };
         st
     }
+
+    /// The chunk path of ranged reads (te_clay_set_range_chunk_path, off by default): a stripe whose
+    /// window holds exactly one erased data chunk rebuilds that chunk alone on the windowed recover
+    /// class kernels (TE_RANGE_CHUNK) instead of decoding the stripe.  The gateway's small Range
+    /// reads under a degraded track; results are byte-identical either way.
+    pub fn set_range_chunk_path(&mut self, on: bool) -> Result<(), DecodeError> {
+        decode_status(unsafe { ffi::te_clay_set_range_chunk_path(self.raw.as_ptr(), on as std::os::raw::c_int) })
+    }
+
+    pub fn range_chunk_path(&self) -> bool {
+        unsafe { ffi::te_clay_range_chunk_path(self.raw.as_ptr()) != 0 }
+    }
+
+    /// te_slicer_range_plan_ex with the chunk path on: per touched stripe (class, lo, hi, shard), the
+    /// shard rebuilt for a TE_RANGE_CHUNK stripe, u32::MAX otherwise.
+    pub fn range_plan_chunk(&self, cfg: &ObjectCfg, blob_len: u64, avail_mask: u32, start: u64, len: u64)
+                            -> Result<(u64, Vec<(u32, u64, u64, u32)>), DecodeError> {
+        let mut g = ffi::te_geometry { stripe_size: 0, num_stripes: 0, chunk_size: 0, sub_chunk_size: 0, slice_len: 0 };
+        unsafe { ffi::te_slicer_geometry(self.raw.as_ptr(), blob_len as usize, &mut g) };
+        let ns = g.num_stripes.max(1) as usize;
+        let (mut first, mut cnt) = (0u64, 0u64);
+        let (mut cls, mut lo, mut hi, mut sh) = (vec![0u32; ns], vec![0u64; ns], vec![0u64; ns], vec![u32::MAX; ns]);
+        let c = cfg.ffi();
+        let r = unsafe {
+            ffi::te_slicer_range_plan_ex(self.raw.as_ptr(), &c, blob_len, avail_mask, start, len, 1, &mut first, &mut cnt,
+                                         cls.as_mut_ptr(), lo.as_mut_ptr(), hi.as_mut_ptr(), sh.as_mut_ptr())
+        };
+        decode_status(r).map(|_| (first, (0..cnt as usize).map(|i| (cls[i], lo[i], hi[i], sh[i])).collect()))
+    }
+
+    /// The chunk path's share of the handle's last ranged read (te_clay_range_chunk_launch_stats).
+    pub fn range_chunk_launch_stats(&mut self) -> ffi::te_range_chunk_stats {
+        let mut st = ffi::te_range_chunk_stats { stripes_rebuilt: 0, gather_jobs: 0, bytes_stored: 0 };
+        unsafe { ffi::te_clay_range_chunk_launch_stats(self.raw.as_ptr(), &mut st) };
+        st
+    }
 }
 
 /// RepairPlan (repair.rs:16-28) with the reference's public fields, read back from the library's

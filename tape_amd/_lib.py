@@ -78,7 +78,11 @@ class te_range_launch_stats(C.Structure):
                                           "bytes_staged")]
 
 
-RANGE_COPY, RANGE_DECODE = 0, 1  # TE_RANGE_COPY / TE_RANGE_DECODE
+class te_range_chunk_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("stripes_rebuilt", "gather_jobs", "bytes_stored")]
+
+
+RANGE_COPY, RANGE_DECODE, RANGE_CHUNK = 0, 1, 2  # TE_RANGE_COPY / TE_RANGE_DECODE / TE_RANGE_CHUNK
 
 
 class te_recover_object(C.Structure):
@@ -253,6 +257,11 @@ def _load() -> C.CDLL:
                                              sz, vp, vp]),
         "te_slicer_decode_range": (i, [vp, C.POINTER(te_slicer_cfg), pp, sz, u64, u64, u8p, sz, szp]),
         "te_clay_range_launch_stats": (i, [vp, C.POINTER(te_range_launch_stats)]),
+        "te_slicer_range_plan_ex": (i, [vp, C.POINTER(te_slicer_cfg), u64, u32, u64, u64, i, C.POINTER(u64),
+                                        C.POINTER(u64), C.POINTER(u32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u32)]),
+        "te_clay_set_range_chunk_path": (i, [vp, i]),
+        "te_clay_range_chunk_path": (i, [vp]),
+        "te_clay_range_chunk_launch_stats": (i, [vp, C.POINTER(te_range_chunk_stats)]),
         "te_repair_batch_device": (i, [vp, vp, C.POINTER(te_repair_object), sz, vp, vp]),
         "te_recover_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_object), u8p, sz,
                                         vp, vp]),

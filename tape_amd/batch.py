@@ -327,6 +327,25 @@ def range_launch_stats(coder: ClayCoder) -> dict:
     return {f: int(getattr(st, f)) for f, _ in st._fields_}
 
 
+def set_range_chunk_path(coder: ClayCoder, on: bool) -> None:
+    """te_clay_set_range_chunk_path: ranged reads rebuild a window's lone erased data chunk on the
+    windowed recover class kernels (TE_RANGE_CHUNK) instead of decoding the stripe.  Off by default."""
+    _check(lib.te_clay_set_range_chunk_path(coder.handle, 1 if on else 0), "decode")
+
+
+def range_chunk_path(coder: ClayCoder) -> bool:
+    """te_clay_range_chunk_path: the handle's knob."""
+    return bool(lib.te_clay_range_chunk_path(coder.handle))
+
+
+def range_chunk_launch_stats(coder: ClayCoder) -> dict:
+    """te_clay_range_chunk_launch_stats: the chunk path's share of the handle's last ranged call --
+    stripes rebuilt, their gather jobs, bytes the windowed recover jobs stored (zero with the knob off)."""
+    st = _lib.te_range_chunk_stats()
+    _check(lib.te_clay_range_chunk_launch_stats(coder.handle, C.byref(st)), "decode")
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+
 def recover_batch(slicer: Slicer, slices, objs: list[tuple[int, int, int, int, int]], metas: bytes, out,
                   stream=None) -> None:
     """Node recover (recover.rs:411-442 `reconstruct`) on the device: objs are (slices_off,

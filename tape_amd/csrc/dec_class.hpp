@@ -39,6 +39,19 @@ namespace tec {
 // first among its column's erased nodes (dec_class_lost_first, with the matrix rows), and the
 // representative's lost node is the first erased node of column yL.
 constexpr int kDecClassN = 20, kDecClassK = 7, kDecClassesDecode = 8, kDecClasses = 24;
+// Windowed recover kernels (a ranged read's lone erased data chunk, te_clay_set_range_chunk_path):
+// the eight "lost node in column 0" recover classes 8 + 2 a0 built a second time with CTile's
+// window clip (TEC_DCLS_WINDOW=1), so a job stores only bytes [out_lo, out_len) of the lost chunk.
+// Data nodes are all in column 0, so the column-1 classes have no windowed form.  They are kernels
+// of the same classes, not new classes: registry ids kDecClasses + a0, reported under 8 + 2 a0.
+constexpr int kDecClassesWin = 8, kDecClassKernels = kDecClasses + kDecClassesWin;
+inline int dec_class_win_id(int id) {  // recover class 8 + 2 a0 -> its windowed kernel's registry id, or -1
+    return id >= kDecClassesDecode && id < kDecClasses && (id - kDecClassesDecode) % 2 == 0
+               ? kDecClasses + (id - kDecClassesDecode) / 2 : -1;
+}
+inline int dec_class_base_id(int id) {  // a registry id -> the class it runs (identity below kDecClasses)
+    return id >= kDecClasses && id < kDecClassKernels ? kDecClassesDecode + 2 * (id - kDecClasses) : id;
+}
 constexpr int kDecClassSplit = 4;  // per-call kernel: waves sharing one 64-column group
 constexpr uint64_t kDecClassOutMask = 0x3ffull;  // decode: every column-0 node is an output
 
@@ -153,8 +166,13 @@ struct DecClassGenOpt {
 };
 
 // nring_out: the per-call kernel's ring rows per step, as the kernel registers them.
+// win (a column-0 recover class only): the windowed kernels dec_class_<id>_win[_small], the same
+// program with the lost chunk's output base taken relative to the job's out_lo.
 inline std::string dec_class_source(const ClayHost &h, int id, uint8_t t_u, DecProgHdr &Hout,
-                                    const DecClassGenOpt &opt = DecClassGenOpt(), uint32_t *nring_out = nullptr) {
+                                    const DecClassGenOpt &opt = DecClassGenOpt(), uint32_t *nring_out = nullptr,
+                                    bool win = false) {
+    if (win && dec_class_win_id(id) < 0) return std::string();
+    const char *sfx = win ? "_win" : "";
     GpePattern P;
     DecProgHdr H;
     std::vector<DecStep> steps;
@@ -184,6 +202,7 @@ inline std::string dec_class_source(const ClayHost &h, int id, uint8_t t_u, DecP
     emit("// generated by gen_dec_class (dec_class.hpp): class %d = %d known column-0 nodes, %s, %d steps, %u slots, "
          "%u scratch rows\n", id, cs.a0, cs.yl < 0 ? "decode" : cs.yl == 0 ? "recover, lost node in column 0" :
          "recover, lost node in column 1", NS, H.nslots, H.nscratch);
+    if (win) s += "// windowed: stores only bytes [out_lo, out_len) of the lost chunk (build with TEC_DCLS_WINDOW=1)\n";
     s += "#include \"decode_class_dev.hpp\"\nnamespace tec {\nnamespace dcls {\n";
     // One body, two kernels: the batch kernel (G = 2 waves per workgroup, the register budget of
     // opt.wpe waves per SIMD, each step's input loads issued one step ahead) and the per-call
@@ -211,10 +230,10 @@ inline std::string dec_class_source(const ClayHost &h, int id, uint8_t t_u, DecP
     const uint32_t ring0 = 0, slot0 = small ? 2 * nring : 0u, scr0 = small ? 2 * nring + H.nslots : 0u;
     if (small)
         emit("__global__ void __attribute__((amdgpu_flat_work_group_size(1, %d), amdgpu_waves_per_eu(1)))\n"
-             "dec_class_%d_small(DecClassArgs a) {\n  constexpr int G = 1;\n", 64 * (W + 1), id);
+             "dec_class_%d%s_small(DecClassArgs a) {\n  constexpr int G = 1;\n", 64 * (W + 1), id, sfx);
     else
         emit("__global__ void __attribute__((amdgpu_flat_work_group_size(1, 128), amdgpu_waves_per_eu(%d)))\n"
-             "dec_class_%d(DecClassArgs a) {\n  constexpr int G = 2;\n", opt.wpe, id);
+             "dec_class_%d%s(DecClassArgs a) {\n  constexpr int G = 2;\n", opt.wpe, id, sfx);
     emit("  extern __shared__ __attribute__((aligned(16))) u32 lds[];\n  CTile<G, %d> T(a, reinterpret_cast<u8 *>(lds));\n", W);
     // per-workgroup offsets: known slices, plane digits, data chunks (only what the program uses;
     // the rest is dead code)
@@ -222,11 +241,12 @@ inline std::string dec_class_source(const ClayHost &h, int id, uint8_t t_u, DecP
     for (int x = 0; x < 10; x++) emit("  const u32 pz0_%d = %s * 10u * T.sc;\n", x, phys(x).c_str());
     for (int x = 0; x < 10; x++) emit("  const u32 pz1_%d = (%s - 10u) * T.sc;\n", x, phys(10 + x).c_str());
     // decode: column-0 outputs, a data chunk or dropped (a parity node: an offset past the range);
-    // recover: the lost node's chunk is the job's whole output
+    // recover: the lost node's chunk is the job's whole output (windowed: relative to the
+    // window's start, as out_base -- a store below out_lo wraps past the buffer's range)
     if (cs.yl < 0)
         for (int x = 0; x < 10; x++) emit("  const u32 ob%d = T.out_base(%s);\n", x, phys(x).c_str());
     else
-        emit("  const u32 ob%d = 0u;\n", cs.yl == 0 ? cs.a0 : 10 + (kDecClassK - cs.a0));
+        emit("  const u32 ob%d = %s;\n", cs.yl == 0 ? cs.a0 : 10 + (kDecClassK - cs.a0), win ? "T.lost_base()" : "0u");
     auto poff = [&](uint32_t z) {
         return "pz0_" + std::to_string(z / 10) + " + pz1_" + std::to_string(z % 10);
     };
@@ -462,9 +482,9 @@ inline std::string dec_class_source(const ClayHost &h, int id, uint8_t t_u, DecP
     };
     body(true);
     body(false);
-    emit("void dec_class_reg_%d(DecClassEntry &e) {\n  e.fn[0] = reinterpret_cast<const void *>(&dec_class_%d_small);\n"
-         "  e.fn[1] = reinterpret_cast<const void *>(&dec_class_%d);\n  e.nslots = %uu;\n  e.nscratch = %uu;\n"
-         "  e.nring = %uu;\n}\n", id, id, id, H.nslots, H.nscratch, nring);
+    emit("void dec_class_reg_%d%s(DecClassEntry &e) {\n  e.fn[0] = reinterpret_cast<const void *>(&dec_class_%d%s_small);\n"
+         "  e.fn[1] = reinterpret_cast<const void *>(&dec_class_%d%s);\n  e.nslots = %uu;\n  e.nscratch = %uu;\n"
+         "  e.nring = %uu;\n}\n", id, sfx, id, sfx, id, sfx, H.nslots, H.nscratch, nring);
     s += "}  // namespace dcls\n}  // namespace tec\n";
     return s;
 }

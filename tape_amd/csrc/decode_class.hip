@@ -10,15 +10,17 @@ namespace dcls {
 
 static const dcls::DecClassEntry *dec_class_table() {
     static const dcls::DecClassEntry *t = [] {
-        static dcls::DecClassEntry e[kDecClasses];
-        for (int i = 0; i < kDecClasses; i++) dcls::kDecClassReg[i](e[i]);
+        // the classes, then the windowed kernels of the column-0 recover classes (dec_class_win_id)
+        static_assert(sizeof(dcls::kDecClassReg) / sizeof(dcls::kDecClassReg[0]) == kDecClassKernels, "registry size");
+        static dcls::DecClassEntry e[kDecClassKernels];
+        for (int i = 0; i < kDecClassKernels; i++) dcls::kDecClassReg[i](e[i]);
         return e;
     }();
     return t;
 }
 
 bool dec_class_info(int id, uint32_t *nslots, uint32_t *nscratch) {
-    if (id < 0 || id >= kDecClasses) return false;
+    if (id < 0 || id >= kDecClassKernels) return false;
     const dcls::DecClassEntry &e = dec_class_table()[id];
     if (!e.fn[0] || !e.fn[1]) return false;
     if (nslots) *nslots = e.nslots;
@@ -41,7 +43,7 @@ size_t dec_class_scratch_bytes(int id, uint32_t njobs, uint32_t sc, uint32_t G) 
 hipError_t launch_dec_class(int id, const GpeJob *jobs, const GpePattern *patterns, uint32_t njobs, uint32_t sc,
                             uint64_t in_stride, uint64_t out_stride, uint32_t n, uint8_t *scratch, uint32_t G,
                             hipStream_t s) {
-    const DecClassSpec spec = dec_class_spec(id);
+    const DecClassSpec spec = dec_class_spec(dec_class_base_id(id));  // a windowed kernel: its class's
     if (njobs == 0) return hipSuccess;
     uint32_t nslots = 0, nscr = 0;
     if (!dec_class_info(id, &nslots, &nscr) || (G != 1 && G != 2) || sc < 8 || n != (uint32_t)kDecClassN)

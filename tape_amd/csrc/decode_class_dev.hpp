@@ -82,8 +82,9 @@ struct CTile {
         // so the buffer range check drops a store below out_lo exactly as it drops one past
         // out_len, and a job without a window pays the same two compares per store as before
         // (out_st_oob; a windowed stripe pays a third for each word outside its window).  The
-        // node-recover classes never run a windowed job and are built with TEC_DCLS_WINDOW=0
-        // (Makefile, scripts/build_class_var.sh).
+        // node-recover classes' kernels never run a windowed job and are built with
+        // TEC_DCLS_WINDOW=0 (Makefile, scripts/build_class_var.sh); a ranged read's lone erased
+        // chunk runs the `_win` kernels of the column-0 recover classes, built with 1 (lost_base).
         olo = TEC_DCLS_WINDOW ? (u32)J.out_lo : 0u;
         olen = (u32)J.out_len - olo;
         // every output row inside the job's output share (not a last stripe, not a window)
@@ -126,6 +127,10 @@ struct CTile {
     // every stripe's output range, so the buffer range check drops its stores
     // (relative to the window's start, see the constructor)
     __device__ __forceinline__ u32 out_base(u32 node) const { return node < kData ? node * out_stride - olo : kDropBase; }
+    // output base of a windowed recover job's lost node (dec_class_<id>_win): the job's `out` is
+    // the lost chunk's byte 0, so the chunk starts out_lo below the window (olo < the chunk size
+    // < 2^31: never kDropBase)
+    __device__ __forceinline__ u32 lost_base() const { return 0u - olo; }
     static constexpr u32 kData = 7, kDropBase = 0x80000000u, kBelow = 0xFFFFFFFDu;
     // one decoded word to data chunk offset `ob` at plane offset `po`, where it was loaded; a
     // word that is not wholly inside the output range -- across the end of the stripe's share, or

@@ -542,6 +542,10 @@ struct te_clay {
     te_decode_launch_stats dls{};
     // the last ranged call's stripe outcomes (te_clay_range_launch_stats), zeroed by its entry point
     te_range_launch_stats rgs{};
+    // te_clay_set_range_chunk_path: a ranged read's lone erased data chunk on the windowed recover
+    // class kernels (off by default), and the last ranged call's share of it
+    int range_chunk = 0;
+    te_range_chunk_stats rcs{};
     // the same for the encode_enqueue / repair_enqueue launches of the last encode / repair call
     te_encode_launch_stats els{};
     te_repair_launch_stats rls{};
@@ -1171,6 +1175,9 @@ struct DecItem {          // one object, host-validated
     bool ranged = false;
     uint64_t w_start = 0, w_len = 0;
     uint64_t in_skew = 0;  // the slices at in_base start at slice byte in_skew (te_slicer_decode_range's staging)
+    // ranged read: a stripe whose window holds exactly one erased data chunk rebuilds that chunk
+    // alone (TE_RANGE_CHUNK: the handle's knob, and range_chunk_ok of the object)
+    bool chunk = false;
 };
 
 // Ranged reads (te_slicer_range_plan): the stripes a window touches, [sb, se)
@@ -1183,7 +1190,8 @@ inline void range_stripes(uint64_t S, uint64_t start, uint64_t len, uint64_t &sb
 // ... and the window inside stripe st, [lo, hi) in stripe bytes.  copy: every data chunk it
 // intersects (chunk x = stripe bytes [x cs, (x + 1) cs), shard x) is a present slice's -- decided
 // from the mask itself, not from the padded erasure set -- so nothing needs decoding.
-struct RangeWin { uint64_t lo, hi; bool copy; };
+// miss: the absent chunks among them, and the last one (the only one when miss == 1).
+struct RangeWin { uint64_t lo, hi; bool copy; uint32_t miss = 0, miss_x = 0; };
 RangeWin range_window(int n, int rotated, uint32_t avail, uint64_t blob_len, uint64_t S, uint64_t cs, uint64_t st,
                       uint64_t start, uint64_t len) {
     const uint64_t base = st * S, end = std::min({start + len, base + S, blob_len});
@@ -1192,9 +1200,26 @@ RangeWin range_window(int n, int rotated, uint32_t avail, uint64_t blob_len, uin
     w.hi = end - base;
     w.copy = true;
     for (uint64_t x = w.lo / cs; x * cs < w.hi; x++)
-        if (!((avail >> te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)x)) & 1u)) w.copy = false;
+        if (!((avail >> te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)x)) & 1u)) {
+            w.copy = false;
+            w.miss++;
+            w.miss_x = (uint32_t)x;
+        }
     return w;
 }
+// The chunk path (TE_RANGE_CHUNK) is open to an object where a node recover of its stripes runs a
+// class kernel: Clay(20,7,16), the class kernels not switched off (measurement knob), sub-chunks
+// of >= 8 bytes and 31-bit slice / share offsets (decode_enqueue's staged_group, on the object's
+// own slice length).  Host only: te_slicer_range_plan_ex answers from the same rule.
+bool range_chunk_ok(const ClayHost &h, uint64_t cs, uint64_t slice_len) {
+    static const bool class_on = [] {
+        const char *e = tec_knob("TEC_DEC_CLASS");
+        return !(e && e[0] == '0');
+    }();
+    if (!class_on || h.n != kDecClassN || h.k != kDecClassK || h.q != kRepQ || h.t != 2 || h.nu != 0) return false;
+    return cs / (uint64_t)h.alpha >= 8 && (uint64_t)h.n * slice_len < 0x7fffffffull && cs * (uint64_t)h.k < 0x7fffffffull;
+}
+inline bool range_is_chunk(const DecItem &it, const RangeWin &w) { return it.chunk && w.miss == 1; }
 // every touched stripe's window, stripe sb + i at [i]
 std::vector<RangeWin> range_windows(int n, int rotated, uint32_t avail, uint64_t blob_len, uint64_t S, uint64_t cs,
                                     uint64_t start, uint64_t len) {
@@ -1427,7 +1452,8 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
                 if (it.ranged && wins[i][st - sb].copy) continue;
                 const uint64_t emask = stripe_emask(h, rotated, it.avail, st);
                 const int onode = it.lost >= 0 ? h.ext_to_int((int)te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st,
-                                                                                      (uint32_t)it.lost)) : -1;
+                                                                                      (uint32_t)it.lost))
+                                  : it.ranged && range_is_chunk(it, wins[i][st - sb]) ? h.ext_to_int((int)wins[i][st - sb].miss_x) : -1;
                 if (seen.emplace(dec_key(emask, onode), 1).second) keys.push_back({emask, onode});
             }
         }
@@ -1444,7 +1470,10 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
     uint32_t max_er = 0;
     // ranged reads: a copy stripe's window is gathered from the present data chunks (one launch
     // for the call), a decode stripe's job carries its window [out_lo, out_len)
+    // a chunk stripe (TE_RANGE_CHUNK): the present chunks' pieces join the gather, the one erased
+    // chunk's piece is a windowed recover job of its own groups (by chunk size, as `groups`)
     std::vector<CopyJob> copies;
+    std::map<uint64_t, std::vector<GpeJob>> chunk_groups;
     bool ranged_call = false;
     for (size_t i = 0; i < nitems; i++) {
         const DecItem &it = items[i];
@@ -1453,12 +1482,16 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
         ranged_call = ranged_call || it.ranged;
         for (uint64_t st = sb; st < se; st++) {
             RangeWin win{0, 0, false};
+            bool chunk = false;  // rebuild chunk win.miss_x alone
             if (it.ranged) {
                 win = wins[i][st - sb];
+                chunk = range_is_chunk(it, win);
                 c->rgs.stripes_touched++;
-                if (win.copy) {
-                    c->rgs.stripes_copied++;
+                if (win.copy || chunk) {
+                    if (chunk) c->rcs.stripes_rebuilt++;
+                    else c->rgs.stripes_copied++;
                     for (uint64_t x = win.lo / it.cs; x * it.cs < win.hi; x++) {
+                        if (chunk && x == win.miss_x) continue;
                         const uint64_t a = std::max(win.lo, x * it.cs), b = std::min(win.hi, (x + 1) * it.cs);
                         const uint32_t sl = te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)x);
                         CopyJob cj{};
@@ -1466,15 +1499,19 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
                         cj.dst = d_out + it.out_off + (st * it.stripe + a - it.w_start);
                         cj.len = cj.valid = b - a;
                         copies.push_back(cj);
+                        c->rcs.gather_jobs += chunk;
                     }
-                    continue;
+                    if (!chunk) continue;
+                } else {
+                    c->rgs.stripes_decoded++;
                 }
-                c->rgs.stripes_decoded++;
             }
             const uint64_t emask = stripe_emask(h, rotated, it.avail, st);
+            // the output node: recover's lost slice's shard, a chunk stripe's erased data shard
             const int onode = it.lost >= 0 ? h.ext_to_int((int)te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st,
-                                                                                  (uint32_t)it.lost)) : -1;
-            fused = fused || onode >= 0;
+                                                                                  (uint32_t)it.lost))
+                              : chunk ? h.ext_to_int((int)win.miss_x) : -1;
+            fused = fused || it.lost >= 0;
             const uint64_t pkey = emask | (uint64_t)(onode + 1) << 48;
             auto f = pat_index.find(pkey);
             uint32_t pid;
@@ -1492,7 +1529,15 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
             GpeJob g{};
             g.in = d_slices + it.in_base + (st * it.cs - it.in_skew);
             g.in_len = ~0ull;
-            if (onode >= 0) {  // the lost slice's chunk of this stripe, whole
+            if (chunk) {
+                // `out` is the address of the erased chunk's byte 0 (below the caller's range when
+                // the window starts inside the chunk), the window [out_lo, out_len) in chunk bytes
+                const uint64_t x0 = win.miss_x * it.cs;
+                g.out = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(d_out) + it.out_off + st * it.stripe + x0 - it.w_start);
+                g.out_lo = std::max(win.lo, x0) - x0;
+                g.out_len = std::min(win.hi, x0 + it.cs) - x0;
+                c->rcs.bytes_stored += g.out_len - g.out_lo;
+            } else if (onode >= 0) {  // the lost slice's chunk of this stripe, whole
                 g.out = d_out + it.out_off + st * it.cs;
                 g.out_len = it.cs;
             } else if (it.ranged) {
@@ -1508,12 +1553,12 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
             g.rot = rotated ? (uint32_t)((st * TE_ROTATION_STEP) % n) : 0u;
             g.pattern = pid;
             auto key = (it.cs << 32) ^ it.slice_len;
-            groups[key].push_back(g);
+            (chunk ? chunk_groups : groups)[key].push_back(g);
             group_in_stride[key] = it.slice_len;
         }
     }
     c->rgs.gather_jobs += copies.size();
-    if (groups.empty()) {  // nothing to decode: a ranged call of copy stripes only (or of nothing)
+    if (groups.empty() && chunk_groups.empty()) {  // nothing to decode: a ranged call of copy stripes only (or of nothing)
         if (copies.empty()) return TE_OK;
         Arena &A = c->dec;
         A.img.clear();
@@ -1661,6 +1706,25 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
         if (!cls_small && cls.size() > (size_t)class_streams && ncls < 1024 && ncls + nall > kDecSmallStripes) {
             for (ClassGrp &cg : cls) groups[cg.key].insert(groups[cg.key].end(), cg.jobs.begin(), cg.jobs.end());
             cls.clear();
+        }
+    }
+    // chunk stripes (TE_RANGE_CHUNK): each on the windowed kernel of its recover class, a launch
+    // per class beside the decode classes' (they never join the table-driven launch above: only
+    // the class kernels clip a recover job's window).  range_chunk_ok admitted the object, so a
+    // missing kernel here is an error, not a reason to decode the stripe another way.
+    for (auto &kv : chunk_groups) {
+        if (!staged || !class_on || !staged_group(kv.first)) return TE_ERR_UNSUPPORTED;
+        int at[kDecClassKernels];
+        std::fill(at, at + kDecClassKernels, -1);
+        for (const GpeJob &g : kv.second) {
+            const int onode = (int)(pat_keys[g.pattern] >> 48) - 1;
+            const int id = dec_class_win_id(dec_class_of(h, cached[g.pattern]->P, onode));
+            if (id < 0 || !dec_class_info(id, nullptr, nullptr)) return TE_ERR_UNSUPPORTED;
+            if (at[id] < 0) {
+                at[id] = (int)cls.size();
+                cls.push_back(ClassGrp{kv.first, id, {}});
+            }
+            cls[(size_t)at[id]].jobs.push_back(g);
         }
     }
     // staged patterns live in the device store (uploaded once per handle), the jobs name slots;
@@ -1864,7 +1928,7 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
             TE_HIP(launch_dec_class(cg.id, A.at<GpeJob>(cg.off), pp, (uint32_t)cg.jobs.size(), sc, group_in_stride[cg.key],
                                     cs, (uint32_t)n, cls_scratch + scr_at, class_g, ss[k % (size_t)ns]));
             scr_at += dec_class_scratch_bytes(cg.id, (uint32_t)cg.jobs.size(), sc, class_g);
-            dls.class_launches[cg.id]++;
+            dls.class_launches[dec_class_base_id(cg.id)]++;  // a windowed kernel under its class
             dls.class_stripes += cg.jobs.size();
         }
         dls.class_g = class_g;
@@ -3409,6 +3473,44 @@ int te_slicer_range_plan(const te_clay *c, const te_slicer_cfg *cfg, uint64_t bl
     return TE_OK;
 }
 
+int te_slicer_range_plan_ex(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
+                            uint64_t start, uint64_t len, int chunk_path, uint64_t *first_stripe, uint64_t *nstripes,
+                            uint32_t *classes, uint64_t *lo, uint64_t *hi, uint32_t *shards) {
+    int r = te_slicer_range_plan(c, cfg, blob_len, avail_mask, start, len, first_stripe, nstripes, classes, lo, hi);
+    if (r) return r;
+    for (uint64_t i = 0; shards && i < *nstripes; i++) shards[i] = UINT32_MAX;
+    if (!chunk_path || *nstripes == 0) return TE_OK;
+    const ClayHost &h = c->h;
+    te_geometry g;
+    if ((r = te_slicer_geometry(c, (size_t)blob_len, &g))) return r;
+    if (!range_chunk_ok(h, g.chunk_size, g.slice_len)) return TE_OK;
+    const uint32_t avail = avail_mask & (h.n >= 32 ? 0xffffffffu : (1u << h.n) - 1u);
+    for (uint64_t i = 0; i < *nstripes; i++) {
+        const RangeWin w = range_window(h.n, cfg->rotated, avail, blob_len, g.stripe_size, g.chunk_size, *first_stripe + i,
+                                        start, len);
+        if (w.miss != 1) continue;
+        if (classes) classes[i] = TE_RANGE_CHUNK;
+        if (shards) shards[i] = w.miss_x;
+    }
+    return TE_OK;
+}
+
+int te_clay_set_range_chunk_path(te_clay *c, int on) {
+    if (!c || (on != 0 && on != 1)) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->range_chunk = on;
+    return TE_OK;
+}
+
+int te_clay_range_chunk_path(const te_clay *c) { return c ? c->range_chunk : 0; }
+
+int te_clay_range_chunk_launch_stats(te_clay *c, te_range_chunk_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->rcs;
+    return TE_OK;
+}
+
 int te_clay_range_launch_stats(te_clay *c, te_range_launch_stats *out) {
     if (!c || !out) return TE_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -3435,6 +3537,9 @@ int te_decode_range_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uin
     std::lock_guard<std::mutex> lk(c->mu);
     c->dls = te_decode_launch_stats{};
     c->rgs = te_range_launch_stats{};
+    c->rcs = te_range_chunk_stats{};
+    if (c->range_chunk)
+        for (size_t i = 0; i < nobj; i++) items[i].chunk = range_chunk_ok(c->h, items[i].cs, objs[i].slice_len);
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     return decode_enqueue(c, cfg, d_slices, items.data(), items.size(), d_out, (hipStream_t)stream, false);
@@ -3914,14 +4019,17 @@ int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     std::lock_guard<std::mutex> lk(c->mu);
     c->dls = te_decode_launch_stats{};
     c->rgs = te_range_launch_stats{};
+    c->rcs = te_range_chunk_stats{};
     if (len == 0) return TE_OK;
+    it.chunk = c->range_chunk && range_chunk_ok(h, it.cs, slice_len);
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     r = ensure_stream(c);
     if (r) return r;
     // The staging holds, per slice, only the touched stripes' chunks: slice i's bytes
     // [sb cs, se cs) at i * T.  Of those, a decode stripe stages the chunks of the k slices its
-    // (padded) pattern reads, a copy stripe the present data-chunk bytes inside the window.
+    // (padded) pattern reads, a copy stripe the present data-chunk bytes inside the window, a
+    // chunk stripe both: its recover job's k chunks and the other present pieces of the window.
     uint64_t sb, se;
     range_stripes(it.stripe, start, len, sb, se);
     const uint64_t T = (se - sb) * it.cs;
@@ -3937,7 +4045,7 @@ int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
         c->rgs.bytes_staged += bytes;
     };
     const std::vector<RangeWin> wins = range_windows(n, rotated, avail, it.blob_len, it.stripe, it.cs, start, len);
-    std::vector<uint64_t> emasks(wins.size(), 0);  // the decode stripes' padded erasure sets
+    std::vector<uint64_t> emasks(wins.size(), 0);  // the decode and chunk stripes' padded erasure sets
     for (size_t i = 0; i < wins.size(); i++)
         if (!wins[i].copy) emasks[i] = stripe_emask(h, rotated, avail, sb + i);
     for (int sl = 0; sl < n; sl++) {  // slice-major, so a slice's consecutive chunks merge into one piece
@@ -3945,11 +4053,12 @@ int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
         for (uint64_t st = sb; st < se; st++) {
             const uint32_t sh = te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)sl);
             const RangeWin &w = wins[st - sb];
-            if (w.copy) {
+            const bool read = !w.copy && !((emasks[st - sb] >> h.ext_to_int((int)sh)) & 1ull);  // one of the pattern's k
+            if (read) {
+                stage((uint32_t)sl, st * it.cs, it.cs);
+            } else if (w.copy || range_is_chunk(it, w)) {
                 const uint64_t a = std::max(w.lo, sh * it.cs), b = std::min(w.hi, (sh + 1) * it.cs);
                 if ((int)sh < h.k && a < b) stage((uint32_t)sl, st * it.cs + (a - sh * it.cs), b - a);
-            } else if (!((emasks[st - sb] >> h.ext_to_int((int)sh)) & 1ull)) {
-                stage((uint32_t)sl, st * it.cs, it.cs);
             }
         }
     }

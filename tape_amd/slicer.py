@@ -639,6 +639,29 @@ class Slicer:
         _check(r, "decode")
         return int(first.value), [(int(cls[i]), int(lo[i]), int(hi[i])) for i in range(cnt.value)]
 
+    def range_plan_ex(self, blob_len: int, avail_mask: int, start: int, length: int, chunk_path: bool = True):
+        """te_slicer_range_plan_ex (host only): (first_stripe, [(class, lo, hi, shard) per touched
+        stripe]).  With chunk_path the class is _lib.RANGE_CHUNK where a ranged call with the chunk
+        path on rebuilds one data chunk, and shard is that chunk's shard; else shard is None and
+        the classes are range_plan's."""
+        ns = max(1, int(self.geometry(blob_len).num_stripes))
+        first, cnt = C.c_uint64(), C.c_uint64()
+        cls, lo, hi, sh = (C.c_uint32 * ns)(), (C.c_uint64 * ns)(), (C.c_uint64 * ns)(), (C.c_uint32 * ns)()
+        cfg = self._cfg()
+        r = lib.te_slicer_range_plan_ex(self.coder.handle, C.byref(cfg), blob_len, avail_mask, start, length,
+                                        1 if chunk_path else 0, C.byref(first), C.byref(cnt), cls, lo, hi, sh)
+        _check(r, "decode")
+        return int(first.value), [(int(cls[i]), int(lo[i]), int(hi[i]), None if sh[i] == 0xFFFFFFFF else int(sh[i]))
+                                  for i in range(cnt.value)]
+
+    def set_range_chunk_path(self, on: bool) -> None:
+        """te_clay_set_range_chunk_path on this slicer's coder (decode_range then rebuilds a window's
+        lone erased data chunk alone).  Off by default."""
+        _check(lib.te_clay_set_range_chunk_path(self.coder.handle, 1 if on else 0), "decode")
+
+    def range_chunk_path(self) -> bool:
+        return bool(lib.te_clay_range_chunk_path(self.coder.handle))
+
     def decode_verified(self, chunks: list[tuple[int, bytes]], leaves) -> tuple[bytes, list[int]]:
         """Slicer::decode behind the gateway's check (network/gateway/src/http/handlers/object/
         decode.rs:121-139): a slice enters the decode only if hash_leaf(slice) == leaves[index].
