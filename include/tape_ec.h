@@ -745,6 +745,79 @@ typedef struct te_read_launch_stats {
 int te_clay_read_launch_stats(te_clay *c, te_read_launch_stats *out);
 
 /* ------------------------------------------------------------------------------------------
+ * Node rebuild pipeline: the node side's host boundary.  A node that has lost a spool drains
+ * `pending_repairs` in batches of `repair_batch` tracks (network/node/src/features/spool/
+ * repair.rs:94-226), each helper's fragment arriving as one host buffer; tracks that escalate
+ * fetch k full peer slices and `reconstruct` (recover.rs:77-244, 411-442); both end in
+ * verify_slice(position, rebuilt) (repair.rs:340, recover.rs:216) and put_slice.  All pointers
+ * below are HOST pointers; offsets in `objs` are relative to the call's base pointers.
+ * ------------------------------------------------------------------------------------------ */
+/* Host only: the windows the rebuild pipeline cuts a batch into, in the shape of
+ * te_decode_window_plan (cuts, cap, *nwindows, cuts == NULL = count only,
+ * TE_ERR_BUFFER_TOO_SMALL).  Cutting is greedy, in object order, at most window_bytes per window
+ * (0 = 128 MiB); an object above the limit gets a window alone.  A repair object (repair.rs:94-226)
+ * counts as the sum of te_extract_repair_data_size(plan, h) over its plan's helpers in, plus
+ * num_stripes * chunk_size + 48 out; a NULL plan is TE_ERR_INVALID_ARG. */
+int te_repair_window_plan(const te_clay *c, const te_repair_object *objs, size_t nobj, size_t window_bytes,
+                          size_t *cuts, size_t cap, size_t *nwindows);
+/* The same for recover objects (recover.rs:77-244): popcount(avail_mask) * slice_len in, plus
+ * slice_len out. */
+int te_recover_window_plan(const te_clay *c, const te_recover_object *objs, size_t nobj, size_t window_bytes,
+                           size_t *cuts, size_t cap, size_t *nwindows);
+/* The repair loop's batch (repair.rs:94-226, verify_slice at repair.rs:340) HOST -> HOST:
+ * te_repair_batch_device's meaning with helper_off / out_off as offsets into h_helpers / h_out.
+ * Only the fragments of the helpers a plan names are read and uploaded (packed; the other entries of
+ * helper_off are ignored).  h_leaves: nobj * n * 32 bytes, or NULL for the unverified form (h_ok may
+ * then be NULL).  Verified: h_ok[o] = 1 if hash_leaf(repaired) == leaves[plan.lost], else 0; the
+ * repaired bytes are written either way and the caller escalates an object whose h_ok is 0.  The
+ * unverified form does not write h_ok.  Every object is validated before anything is enqueued and
+ * before the call looks for a device: te_repair_batch_device's checks (a NULL plan or a plan of
+ * another profile: TE_ERR_INVALID_ARG), and here up front what that call finds while it enqueues: a
+ * named helper whose helper_off is UINT64_MAX is TE_ERR_MISSING_HELPER.  The windows of
+ * te_repair_window_plan run over the handle's three pipeline streams.  The leaf hashes follow
+ * te_set_commit_hashing per window, as te_decode_verified_batch_host's do: TE_HASH_HOST hashes the
+ * repaired slices on the host pool after their D2H copy has landed, TE_HASH_DEVICE with the
+ * leaf-verify kernel before it (a window with a repaired length or an out_off that is no multiple
+ * of 4 is hashed on the host).  Results are identical in every mode.  Pageable buffers go through
+ * page-locked staging; pinned ones (te_host_alloc / te_host_register) are copied directly.  Each of
+ * h_helpers and h_out is of one kind throughout: the call asks once per buffer (h_helpers and h_out
+ * themselves; te_recover_batch_host: the first present slice of h_slices, and h_out).
+ * Synchronous. */
+int te_repair_batch_host(te_clay *c, const uint8_t *h_helpers, const te_repair_object *objs, const uint8_t *h_leaves,
+                         size_t nobj, uint8_t *h_out, uint32_t *h_ok, size_t window_bytes);
+/* The escalation's batch (recover.rs:77-244, `reconstruct` recover.rs:411-442, verify_slice at
+ * recover.rs:216) HOST -> HOST, with te_recover_verified_batch_device's contract: peer slices that
+ * fail their leaf are left out and reported in h_rejected_mask[o]; an object with fewer than k
+ * verified slices gets h_status[o] = TE_ERR_NOT_ENOUGH_SLICES, nothing is written to its output
+ * range and its h_ok is 0; every other is rebuilt, h_ok[o] = 1 if the rebuilt slice hashes to
+ * leaves[lost].  h_leaves == NULL is the unverified form: h_status, h_ok and h_rejected_mask may
+ * then be NULL (h_ok and h_rejected_mask are not written; h_status, if given, is TE_OK throughout),
+ * and fewer than k present slices is the call's error, as in te_recover_batch_device.
+ * Only the slices named in avail_mask are read (absent slots may be unmapped); with host hashing
+ * only the verified slices of objects that rebuild are uploaded.  Any slice_len and offsets: a
+ * window not aligned to 4 is hashed on the host.  Synchronous. */
+int te_recover_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_recover_object *objs,
+                          const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *h_out,
+                          uint32_t *h_rejected_mask, uint32_t *h_ok, int *h_status, size_t window_bytes);
+/* The handle's last te_repair_batch_host / te_recover_batch_host call (repair.rs:94-226,
+ * recover.rs:77-244), zeroed when the call has passed its argument checks.  The kernels of the
+ * call, summed over its windows, stay in te_clay_repair_launch_stats / te_clay_decode_launch_stats. */
+typedef struct te_rebuild_launch_stats {
+    uint64_t windows;               /* pipeline windows */
+    uint64_t objects;               /* objects of those windows */
+    uint64_t pieces_uploaded;       /* repair: helper fragments; recover: peer slices copied to the device */
+    uint64_t bytes_h2d;             /* their bytes (descriptors and leaves not counted) */
+    uint64_t bytes_d2h;             /* rebuilt slice bytes copied back */
+    uint64_t slices_hashed_host;    /* leaf hashes by the host pool (peer and rebuilt slices) */
+    uint64_t slices_hashed_device;  /* leaf hashes by the leaf-verify kernel */
+    uint64_t host_waits;            /* times the host waited for the device inside the pipeline, as in
+                                       te_read_launch_stats: a device-hashed recover window's peer masks,
+                                       and a window's results where the host goes on with them (hashing,
+                                       masks, the scatter out of staging); the final wait is not counted */
+} te_rebuild_launch_stats;
+int te_clay_rebuild_launch_stats(te_clay *c, te_rebuild_launch_stats *out);
+
+/* ------------------------------------------------------------------------------------------
  * OuterCoder (lib/slicer/src/outer.rs:19-197): single-level Reed-Solomon over
  * GF(2^16) in the Leopard construction of reed-solomon-simd 3.1.0 (parity unpinned: the crate
  * is not in the container).  n chunks, any k reconstruct; chunks 0..k-1 are the

@@ -15,6 +15,7 @@ use std::collections::HashMap;
 use std::ptr::NonNull;
 use tapeec_sys as ffi;
 
+pub mod rebuild;
 pub mod slicer_hook;
 pub mod snapshot;
 pub mod stream;

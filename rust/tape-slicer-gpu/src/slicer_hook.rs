@@ -23,7 +23,7 @@ use tapeec_sys as ffi;
 pub struct ObjectCfg { pub rotated: bool, pub encoding: u64, pub params: u64, pub chunk_index: u64 }
 
 impl ObjectCfg {
-    fn ffi(&self) -> ffi::te_slicer_cfg {
+    pub(crate) fn ffi(&self) -> ffi::te_slicer_cfg {
         ffi::te_slicer_cfg { rotated: self.rotated as i32, encoding: self.encoding, params: self.params,
                              chunk_index: self.chunk_index }
     }
@@ -213,6 +213,8 @@ impl Drop for RepairPlan { fn drop(&mut self) { unsafe { ffi::te_repair_plan_fre
 unsafe impl Send for RepairPlan {}
 
 impl RepairPlan {
+    /// The library's plan, for the batch calls' descriptors (rebuild.rs).
+    pub(crate) fn raw(&self) -> *const ffi::te_repair_plan { self.raw }
     /// The pub fields from the library's plan (te_repair_plan_get_info + te_repair_plan_stripe).
     fn wrap(raw: *mut ffi::te_repair_plan) -> Self {
         let mut info = ffi::te_repair_plan_info { lost: 0, num_stripes: 0, d: 0, beta: 0, chunk_size: 0, sub_chunk_size: 0 };

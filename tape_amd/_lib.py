@@ -128,6 +128,11 @@ class te_read_launch_stats(C.Structure):
                                           "slices_hashed_host", "slices_hashed_device", "host_waits")]
 
 
+class te_rebuild_launch_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("windows", "objects", "pieces_uploaded", "bytes_h2d", "bytes_d2h",
+                                          "slices_hashed_host", "slices_hashed_device", "host_waits")]
+
+
 class te_outer_launch_stats(C.Structure):
     _fields_ = [(f, C.c_uint32) for f in ("matrix_launches", "matrix_ptr_launches", "transform_launches",
                                           "low_reg_launches", "decode_launches", "matrix_g", "matrix_kb",
@@ -292,6 +297,12 @@ def _load() -> C.CDLL:
         "te_stream_read_wait": (i, [vp, u64]),
         "te_stream_reader_free": (None, [vp]),
         "te_clay_read_launch_stats": (i, [vp, C.POINTER(te_read_launch_stats)]),
+        "te_repair_window_plan": (i, [vp, C.POINTER(te_repair_object), sz, sz, szp, sz, szp]),
+        "te_recover_window_plan": (i, [vp, C.POINTER(te_recover_object), sz, sz, szp, sz, szp]),
+        "te_repair_batch_host": (i, [vp, vp, C.POINTER(te_repair_object), u8p, sz, vp, u32p, sz]),
+        "te_recover_batch_host": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_object), u8p, u8p, sz, vp,
+                                      u32p, u32p, C.POINTER(i), sz]),
+        "te_clay_rebuild_launch_stats": (i, [vp, C.POINTER(te_rebuild_launch_stats)]),
         "te_outer_chunk_bytes": (sz, [u32, sz]),
         "te_outer_encode": (i, [u32, u32, u8p, sz, u8p, sz, szp]),
         "te_outer_decode": (i, [u32, u32, pp, sz, u8p, sz]),

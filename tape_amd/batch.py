@@ -469,3 +469,76 @@ def repair_verified_batch(coder: ClayCoder, helpers, objs, leaves, out, stream=N
                                             C.c_void_p(out.data_ptr()), ok, _stream_ptr(stream))
     _check(r, "repair")
     return [int(x) for x in ok[:nobj]]
+
+
+def recover_descs(objs: list[tuple[int, int, int, int, int]]):
+    """Prepared te_recover_object array: (slices_off, slice_len, avail_mask, lost, out_off) each."""
+    return (_lib.te_recover_object * max(1, len(objs)))(*[_lib.te_recover_object(*o) for o in objs])
+
+
+def _window_plan(fn, coder: ClayCoder, arr, nobj: int, window_bytes: int, what: str) -> list[int]:
+    nw = C.c_size_t()
+    _check(fn(coder.handle, arr, nobj, window_bytes, None, 0, C.byref(nw)), what)
+    cuts = (C.c_size_t * (nw.value + 1))()
+    _check(fn(coder.handle, arr, nobj, window_bytes, cuts, nw.value + 1, C.byref(nw)), what)
+    return [int(x) for x in cuts[:nw.value + 1]] if nobj else []
+
+
+def repair_window_plan(coder: ClayCoder, objs, window_bytes: int = 0) -> list[int]:
+    """te_repair_window_plan: the cuts of repair_host's windows (window w = objects [cuts[w],
+    cuts[w+1])); host only.  objs as for repair_batch."""
+    arr = objs if _is_desc(objs) else repair_descs(objs)
+    return _window_plan(lib.te_repair_window_plan, coder, arr, len(arr), window_bytes, "repair")
+
+
+def recover_window_plan(coder: ClayCoder, objs, window_bytes: int = 0) -> list[int]:
+    """te_recover_window_plan: the cuts of recover_host's windows; host only.  objs as for
+    recover_batch."""
+    nobj = len(objs)
+    arr = objs if _is_desc(objs) else recover_descs(objs)
+    return _window_plan(lib.te_recover_window_plan, coder, arr, nobj, window_bytes, "recover")
+
+
+def repair_host(coder: ClayCoder, helpers, objs, out, leaves=None, window_bytes: int = 0):
+    """te_repair_batch_host: the node's repair loop (repair.rs:94-226) host -> host, pipelined in
+    windows.  helpers/out are host buffers (numpy arrays or CPU tensors; pinned ones, host_empty,
+    are copied directly); objs as for repair_batch with offsets into them.  With leaves (each
+    object's n leaf hashes) returns ok per object (repair.rs:340), else None; the repaired bytes are
+    written either way.  Who hashes follows set_commit_hashing.  Synchronous."""
+    arr = objs if _is_desc(objs) else repair_descs(objs)
+    nobj = len(arr)
+    lb = _leaf_bytes(leaves, nobj, coder.n()) if leaves is not None else None
+    ok = (C.c_uint32 * max(1, nobj))() if leaves is not None else None
+    r = lib.te_repair_batch_host(coder.handle, C.c_void_p(_host_ptr(helpers)), arr, lb, nobj,
+                                 C.c_void_p(_host_ptr(out)), ok, window_bytes)
+    _check(r, "repair")
+    return [int(x) for x in ok[:nobj]] if ok is not None else None
+
+
+def recover_host(slicer: Slicer, slices, objs, metas: bytes, out, leaves=None, window_bytes: int = 0):
+    """te_recover_batch_host: the escalation (recover.rs:77-244) host -> host, pipelined in windows.
+    objs / metas as for recover_batch with offsets into the host buffers slices/out; only the slices
+    named in each avail_mask are read.  With leaves returns (status, rejected, ok) per object as
+    recover_verified_batch does, else None.  Synchronous."""
+    nobj = len(objs)
+    arr = objs if _is_desc(objs) else recover_descs(objs)
+    cfg = slicer._cfg()
+    verified = leaves is not None
+    lb = _leaf_bytes(leaves, nobj, slicer.coder.n()) if verified else None
+    rej = (C.c_uint32 * max(1, nobj))() if verified else None
+    ok = (C.c_uint32 * max(1, nobj))() if verified else None
+    st = (C.c_int * max(1, nobj))() if verified else None
+    r = lib.te_recover_batch_host(slicer.coder.handle, C.byref(cfg), C.c_void_p(_host_ptr(slices)), arr,
+                                  _meta_bytes(metas), lb, nobj, C.c_void_p(_host_ptr(out)), rej, ok, st, window_bytes)
+    _check(r, "recover")
+    if not verified:
+        return None
+    return [int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]], [int(x) for x in ok[:nobj]]
+
+
+def rebuild_launch_stats(coder: ClayCoder) -> dict:
+    """te_clay_rebuild_launch_stats: windows, objects, uploads, bytes, hashing and host waits of the
+    handle's last repair_host / recover_host call."""
+    st = _lib.te_rebuild_launch_stats()
+    _check(lib.te_clay_rebuild_launch_stats(coder.handle, C.byref(st)), "repair")
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}

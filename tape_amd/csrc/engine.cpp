@@ -434,6 +434,9 @@ bool valid_stripe(uint64_t s) { return s == kStripeSizes[0] || s == kStripeSizes
 // the host read pipeline's per-handle buffers (te_decode_batch_host, below)
 struct ReadPipe;
 void read_pipe_free(ReadPipe *p);
+// and the host rebuild pipeline's (te_repair_batch_host / te_recover_batch_host)
+struct RebuildPipe;
+void rebuild_pipe_free(RebuildPipe *p);
 
 }  // namespace
 
@@ -553,6 +556,9 @@ struct te_clay {
     // calls, as the encode pipeline's are) and the last call's te_read_launch_stats
     ReadPipe *rpipe = nullptr;
     te_read_launch_stats rds{};
+    // te_repair_batch_host / te_recover_batch_host: the same
+    RebuildPipe *rbpipe = nullptr;
+    te_rebuild_launch_stats rbs{};
     // te_snapshot_*: the decode's descriptor arena (payload offsets, segment capacities), its
     // page-locked header read-back, the host forms' device buffers (kept between calls) and the last
     // call's te_snapshot_stats
@@ -578,6 +584,8 @@ static void release_device_state(te_clay *c) {
         if (pe) (void)hipEventDestroy(pe), pe = nullptr;
     read_pipe_free(c->rpipe);
     c->rpipe = nullptr;
+    rebuild_pipe_free(c->rbpipe);
+    c->rbpipe = nullptr;
     c->enc.release();
     c->dec.release();
     c->rep.release();
@@ -3570,8 +3578,10 @@ int te_repair_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair
 // the workspaces are ordered against a previous call on another stream by `rec_done`.
 }  // extern "C"
 // part = a subset of a mixed batch, called from the whole batch's call: the launch stats go on summing
+// locked = the caller holds the handle's lock (the host rebuild pipeline)
 static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_object *objs,
-                         const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool part) {
+                         const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool part,
+                         bool locked = false) {
     if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
     if (nobj == 0) return TE_OK;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
@@ -3623,7 +3633,7 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
                     o.push_back(objs[i]);
                     m.insert(m.end(), h_meta + i * TE_META_SIZE, h_meta + (i + 1) * TE_META_SIZE);
                 }
-                const int r = recover_batch(c, cfg, d_slices, o.data(), m.data(), o.size(), d_out, stream, true);
+                const int r = recover_batch(c, cfg, d_slices, o.data(), m.data(), o.size(), d_out, stream, true, locked);
                 if (r) return r;
             }
             return TE_OK;
@@ -3648,7 +3658,8 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
             for (int k = 0; k < 6; k++) m.words[k] = meta_w[i * 6 + k];
             metas.push_back(m);
         }
-        std::lock_guard<std::mutex> lk(c->mu);
+        std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+        if (!locked) lk.lock();
         DeviceGuard dg(c->device);
         TE_HIP(dg.err);
         hipStream_t s = (hipStream_t)stream;
@@ -3702,7 +3713,8 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
         wins.push_back(w);
         i = w.e;
     }
-    std::lock_guard<std::mutex> lk(c->mu);
+    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    if (!locked) lk.lock();
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     hipStream_t s = (hipStream_t)stream;
@@ -5421,6 +5433,635 @@ void te_stream_reader_free(te_stream_reader *r) {
         d->P = nullptr;
     }
     delete r;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Host rebuild pipeline (te_repair_batch_host, te_recover_batch_host): the node's repair loop
+// (network/node/src/features/spool/repair.rs:94-226) and its escalation (recover.rs:77-244) behind
+// a host boundary, on the read pipeline's plan: windows (rebuild_cuts), window w on slot w mod 3 of
+// the handle's three streams, in three stages:
+//   A  pick who hashes; recover with host hashing: the pool hashes the peer slices where they lie
+//      and the survivor sets are final; enqueue the H2D copies (repair: the plan's fragments,
+//      packed; recover: each slice to its slot of the object's n * slice_len range); recover with
+//      device hashing: the leaves, the verify kernel, the masks' D2H copy and the slot's event;
+//   B  recover with device hashing: wait for that event and pick the survivor sets; enqueue the
+//      repair / recover kernels, device hashing of the rebuilt slices, the D2H copies, and record
+//      the slot's `done` event;
+//   C  wait for `done`; scatter a pageable output out of its staging, hash the rebuilt slices on the
+//      pool (host hashing) or read their masks, and fill h_ok.
+// The driver runs A(w+1), B(w), C(w-1): every wait is spent with later windows' work queued.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+struct RebuildPipe {
+    static constexpr int R = te_clay::kPipe;
+    struct Slot {
+        DevBuf in, out;     // the window's fragments / slices and rebuilt slices
+        DevBuf ver;         // device hashing: expected leaves | digests | peer masks | result masks
+        HostBuf verh;       // its page-locked host side: expected leaves | peer masks | result masks
+        HostBuf hin, hout;  // page-locked staging of pageable caller buffers
+        hipEvent_t peers = nullptr, done = nullptr;
+    } slot[R];
+};
+
+void rebuild_pipe_free(RebuildPipe *p) {  // its streams drained, its device current
+    if (!p) return;
+    for (auto &sl : p->slot) {
+        for (DevBuf *b : {&sl.in, &sl.out, &sl.ver}) b->release();
+        for (HostBuf *b : {&sl.verh, &sl.hin, &sl.hout}) b->release();
+        if (sl.peers) (void)hipEventDestroy(sl.peers);
+        if (sl.done) (void)hipEventDestroy(sl.done);
+    }
+    delete p;
+}
+
+// The bytes of helper `sl`'s fragment under plan p (te_extract_repair_data_size for every slice).
+void plan_needs(const te_repair_plan *p, uint64_t *need) {
+    std::fill(need, need + p->n, 0ull);
+    for (uint32_t st = 0; st < p->ns; st++)
+        for (uint32_t j = 0; j < p->d; j++) need[p->helper_slice[st * p->d + j]] += (uint64_t)p->beta * p->sc;
+}
+
+inline uint64_t plan_out_bytes(const te_repair_plan *p) { return (uint64_t)p->ns * p->cs + TE_META_SIZE; }
+
+void rebuild_cuts(const std::vector<uint64_t> &bytes, size_t window_bytes, std::vector<size_t> &cuts) {
+    if (window_bytes == 0) window_bytes = (size_t)128 << 20;
+    cuts.assign(1, 0);
+    uint64_t sum = 0;
+    for (size_t i = 0; i < bytes.size(); i++) {
+        if (i > cuts.back() && sum + bytes[i] > window_bytes) {
+            cuts.push_back(i);
+            sum = 0;
+        }
+        sum += bytes[i];
+    }
+    if (!bytes.empty()) cuts.push_back(bytes.size());
+}
+
+int repair_object_bytes(const te_clay *c, const te_repair_object *objs, size_t nobj, std::vector<uint64_t> &bytes) {
+    bytes.resize(nobj);
+    uint64_t need[64];
+    for (size_t i = 0; i < nobj; i++) {
+        const te_repair_plan *p = objs[i].plan;
+        if (!p || p->n != (uint32_t)c->h.n || p->n > 64) return TE_ERR_INVALID_ARG;
+        plan_needs(p, need);
+        bytes[i] = plan_out_bytes(p);
+        for (uint32_t sl = 0; sl < p->n; sl++) bytes[i] += need[sl];
+    }
+    return TE_OK;
+}
+
+void recover_object_bytes(const te_clay *c, const te_recover_object *objs, size_t nobj, std::vector<uint64_t> &bytes) {
+    const uint32_t all = slice_bits(c);
+    bytes.resize(nobj);
+    for (size_t i = 0; i < nobj; i++)
+        bytes[i] = ((uint64_t)__builtin_popcount(objs[i].avail_mask & all) + 1u) * objs[i].slice_len;
+}
+
+int cuts_out(const std::vector<size_t> &v, size_t *cuts, size_t cap, size_t *nwindows) {
+    *nwindows = v.size() - 1;
+    if (!cuts) return TE_OK;
+    if (cap < v.size()) return TE_ERR_BUFFER_TOO_SMALL;
+    memcpy(cuts, v.data(), v.size() * sizeof(size_t));
+    return TE_OK;
+}
+
+// One window: nobj objects of the caller's arrays (already offset to the window's first object).
+struct RebuildWin {
+    const te_repair_object *rep = nullptr;   // repair window
+    const te_recover_object *rec = nullptr;  // recover window
+    te_slicer_cfg cfg{};
+    const uint8_t *h_in = nullptr, *h_meta = nullptr, *h_leaves = nullptr;  // h_leaves null: unverified
+    uint8_t *h_out = nullptr;
+    size_t nobj = 0;
+    uint32_t *h_rej = nullptr, *h_ok = nullptr;
+    int *h_status = nullptr;
+    const int *pre = nullptr;  // verified recover: each object's outcome on its present slices
+    int mode = TE_HASH_AUTO;
+    bool pinned_in = false, pinned_out = false;
+    // measurement option TEC_DEBUG_KNOBS=1 TEC_REBUILD_COPY_ONLY=1 (scripts/rebuild_bench.py): the
+    // window's copies with no hashing and no kernels -- the ceiling of the pipeline on a box
+    bool copy_only = false;
+    // stage A -> B -> C
+    bool device_hash = false, resolved = false;
+    std::vector<uint64_t> in_base;               // recover: object o's slice 0 in the slot's input
+    std::vector<uint64_t> frag_off;              // repair: object o's helper_off[] on the device, o * n + slice
+    std::vector<uint32_t> good;                  // recover: the slices that go up / rebuild from
+    std::vector<size_t> run;                     // the objects that rebuild
+    std::vector<uint64_t> out_dev, out_len, out_host;  // per object: its rebuilt slice on the device / host
+    std::vector<uint32_t> lost;
+    std::vector<CopyRun> hout;
+    uint64_t out_sz = 0, npeers = 0;
+};
+
+struct HashItem { const uint8_t *p; uint64_t len; const uint8_t *expect; };
+
+// hash_leaf of the items on the host pool against their expected hashes; waits for the pool.
+void hash_items_host(const std::vector<HashItem> &items, int device, std::vector<uint8_t> &okv) {
+    okv.assign(items.size(), 0);
+    if (items.empty()) return;
+    hh::Pool &pool = hh::Pool::get();
+    const int lanes = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.lanes(), items.size() / (size_t)std::max(1, pool.threads())));
+    auto ok = std::make_shared<std::vector<uint8_t>>(items.size(), 0);
+    auto job = std::make_shared<hh::Job>();
+    std::vector<std::function<void()>> tasks;
+    for (size_t j0 = 0; j0 < items.size();) {
+        size_t j1 = j0 + 1;  // a task's lanes hash messages of one length
+        while (j1 < items.size() && j1 - j0 < (size_t)lanes && items[j1].len == items[j0].len) j1++;
+        std::vector<HashItem> part(items.begin() + (ptrdiff_t)j0, items.begin() + (ptrdiff_t)j1);
+        tasks.push_back([part, j0, ok, job] {
+            const int L = (int)part.size();
+            uint8_t dig[hh::kMaxLanes][TE_HASH_SIZE];
+            const uint8_t *src[hh::kMaxLanes];
+            uint8_t *dst[hh::kMaxLanes];
+            for (int l = 0; l < L; l++) {
+                src[l] = part[(size_t)l].p;
+                dst[l] = dig[l];
+            }
+            hh::hash_leaves(L, src, part[0].len, dst);
+            for (int l = 0; l < L; l++) (*ok)[j0 + (size_t)l] = memcmp(dig[l], part[(size_t)l].expect, TE_HASH_SIZE) == 0;
+            job->done();
+        });
+        j0 = j1;
+    }
+    job->add((int64_t)tasks.size());
+    pool.submit_after(nullptr, device, std::move(tasks));
+    (void)job->wait();
+    okv = *ok;
+}
+
+// The window's H2D copies: pinned memory directly, pageable memory gathered by the copy pool into
+// the slot's page-locked staging first (one DMA per run instead of one driver-staged copy).
+int rebuild_upload(te_clay *c, RebuildPipe::Slot &sl, const RebuildWin &W, const std::vector<CopyRun> &runs, hipStream_t s) {
+    uint8_t *const d_in = sl.in.as<uint8_t>();
+    if (W.pinned_in) return copy_runs(runs, d_in, W.h_in, hipMemcpyHostToDevice, s);
+    uint64_t total = 0;
+    for (const CopyRun &r : runs) total += (r.len + 15) & ~15ull;
+    if (!total) return TE_OK;
+    TE_HIP(sl.hin.ensure(total));
+    std::vector<tec::CopyPool::Seg> segs;
+    std::vector<CopyRun> staged;  // host = offset in the staging
+    uint64_t at = 0;
+    for (const CopyRun &r : runs) {
+        segs.push_back({sl.hin.u8() + at, W.h_in + r.host, (size_t)r.len});
+        if (!staged.empty() && staged.back().host + staged.back().len == at && staged.back().dev + staged.back().len == r.dev)
+            staged.back().len += r.len;
+        else
+            staged.push_back({at, r.dev, r.len});
+        at += (r.len + 15) & ~15ull;
+    }
+    copy_pool(c->device).run(segs);
+    return copy_runs(staged, d_in, sl.hin.u8(), hipMemcpyHostToDevice, s);
+}
+
+// Recover: the survivor sets are known: masks and statuses out, the objects that rebuild and
+// their place in the slot's output buffer.
+void recover_resolve(const te_clay *c, RebuildWin &W) {
+    const uint32_t all = slice_bits(c);
+    W.run.clear();
+    W.hout.clear();
+    W.out_sz = 0;
+    for (size_t o = 0; o < W.nobj; o++) {
+        const uint32_t avail = W.rec[o].avail_mask & all, ok = avail & W.good[o];
+        if (W.h_leaves && W.h_rej) W.h_rej[o] = avail & ~ok;
+        int st = W.pre ? W.pre[o] : TE_OK;
+        DecItem it{};
+        if (!st) st = decode_validate(c, W.h_meta + o * TE_META_SIZE, W.rec[o].slice_len, ok, it);
+        if (W.h_status) W.h_status[o] = st;
+        if (W.h_leaves && W.h_ok) W.h_ok[o] = 0;  // unverified: h_ok is not the call's to write
+        W.good[o] = st ? 0u : ok;
+        if (st) continue;
+        W.run.push_back(o);
+        W.out_dev[o] = W.out_sz;
+        if (!W.hout.empty() && W.hout.back().host + W.hout.back().len == W.out_host[o] &&
+            W.hout.back().dev + W.hout.back().len == W.out_sz)
+            W.hout.back().len += W.out_len[o];
+        else
+            W.hout.push_back({W.out_host[o], W.out_sz, W.out_len[o]});
+        W.out_sz += (W.out_len[o] + 15) & ~15ull;  // device copies 16-byte aligned
+    }
+    W.resolved = true;
+}
+
+// The slot's verify workspace: expected leaves | digests (peers, results) | peer masks | result masks.
+struct VerLayout {
+    size_t exp_b, dig_p, dig_o, mask_b;
+    size_t dig_off() const { return exp_b; }
+    size_t mask_p_off() const { return exp_b + dig_p + dig_o; }
+    size_t mask_o_off() const { return mask_p_off() + mask_b; }
+    size_t total() const { return mask_o_off() + mask_b; }
+    size_t h_mask_p() const { return exp_b; }
+    size_t h_mask_o() const { return exp_b + mask_b; }
+    size_t h_total() const { return exp_b + 2 * mask_b; }
+};
+VerLayout ver_layout(const te_clay *c, const RebuildWin &W) {
+    return VerLayout{W.nobj * (size_t)c->h.n * TE_HASH_SIZE, (size_t)W.npeers * TE_HASH_SIZE, W.nobj * TE_HASH_SIZE,
+                     W.nobj * sizeof(uint32_t)};
+}
+
+// Device hashing: the window's expected leaves and zeroed masks on the device (stage A).
+int rebuild_ver_begin(te_clay *c, RebuildPipe::Slot &sl, const RebuildWin &W, hipStream_t s) {
+    const VerLayout L = ver_layout(c, W);
+    TE_HIP(sl.ver.ensure(L.total()));
+    TE_HIP(sl.verh.ensure(L.h_total()));
+    memcpy(sl.verh.p, W.h_leaves, L.exp_b);
+    TE_HIP(hipMemcpyAsync(sl.ver.p, sl.verh.p, L.exp_b, hipMemcpyHostToDevice, s));
+    TE_HIP(hipMemsetAsync(sl.ver.as<uint8_t>() + L.mask_p_off(), 0, 2 * L.mask_b, s));
+    return TE_OK;
+}
+
+// Stage A of a recover window on slot k (handle locked, its device current).
+int recover_stage_a(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
+    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
+    RebuildPipe::Slot &sl = P.slot[k];
+    const hipStream_t s = read_slot_stream(c, k);
+    te_rebuild_launch_stats &st = c->rbs;
+    st.windows++;
+    st.objects += W.nobj;
+    W.in_base.resize(W.nobj);
+    W.good.assign(W.nobj, 0);
+    W.out_dev.assign(W.nobj, 0);
+    W.out_len.resize(W.nobj);
+    W.out_host.resize(W.nobj);
+    W.lost.resize(W.nobj);
+    uint64_t in_sz = 0, max_slice = 0, slice_bytes = 0, nslices = 0;
+    bool dword = true;
+    for (size_t o = 0; o < W.nobj; o++) {
+        const te_recover_object &ob = W.rec[o];
+        W.in_base[o] = in_sz;
+        in_sz += ((uint64_t)n * ob.slice_len + 15) & ~15ull;
+        W.out_len[o] = ob.slice_len;
+        W.out_host[o] = ob.out_off;
+        W.lost[o] = ob.lost;
+        const uint64_t np = (uint64_t)__builtin_popcount(ob.avail_mask & all);
+        nslices += np;
+        slice_bytes += np * ob.slice_len;
+        if (np) max_slice = std::max<uint64_t>(max_slice, ob.slice_len);
+        dword = dword && ob.slice_len % 4u == 0 && ob.slices_off % 4u == 0 && ob.out_off % 4u == 0;
+    }
+    W.device_hash = W.h_leaves && !W.copy_only && nslices && dword && !host_hash_wins(W.mode, nslices, max_slice, slice_bytes);
+    if (!W.h_leaves || W.copy_only) {
+        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.rec[o].avail_mask & all;
+        recover_resolve(c, W);
+    } else if (!W.device_hash) {
+        std::vector<HashItem> items;
+        std::vector<std::pair<uint32_t, uint32_t>> who;
+        for (size_t o = 0; o < W.nobj; o++)
+            for (uint32_t b = 0; b < n; b++)
+                if (((W.rec[o].avail_mask & all) >> b) & 1u) {
+                    items.push_back({W.h_in + W.rec[o].slices_off + (uint64_t)b * W.rec[o].slice_len, W.rec[o].slice_len,
+                                     W.h_leaves + (o * n + b) * TE_HASH_SIZE});
+                    who.push_back({(uint32_t)o, b});
+                }
+        std::vector<uint8_t> ok;
+        hash_items_host(items, c->device, ok);
+        for (size_t j = 0; j < items.size(); j++)
+            if (ok[j]) W.good[who[j].first] |= 1u << who[j].second;
+        st.slices_hashed_host += items.size();
+        recover_resolve(c, W);
+    } else {
+        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.rec[o].avail_mask & all;  // every present slice goes up
+    }
+    TE_HIP(sl.in.ensure(in_sz + 16));
+    std::vector<CopyRun> hin;
+    std::vector<te_verify_item> vi;
+    for (size_t o = 0; o < W.nobj; o++) {
+        const uint64_t len = W.rec[o].slice_len;
+        for (uint32_t b = 0; b < n; b++) {
+            if (!((W.good[o] >> b) & 1u) || !len) continue;
+            const uint64_t host = W.rec[o].slices_off + (uint64_t)b * len, dev = W.in_base[o] + (uint64_t)b * len;
+            if (!hin.empty() && hin.back().host + hin.back().len == host && hin.back().dev + hin.back().len == dev)
+                hin.back().len += len;
+            else
+                hin.push_back({host, dev, len});
+            st.pieces_uploaded++;
+            st.bytes_h2d += len;
+        }
+        if (W.device_hash) verify_push_slices(vi, o, n, W.in_base[o], len, W.good[o]);
+    }
+    if (int r = rebuild_upload(c, sl, W, hin, s)) return r;
+    if (!W.device_hash) return TE_OK;
+    W.npeers = vi.size();
+    if (int r = rebuild_ver_begin(c, sl, W, s)) return r;
+    const VerLayout L = ver_layout(c, W);
+    uint8_t *const d = sl.ver.as<uint8_t>();
+    uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + L.mask_p_off());
+    if (int r = verify_enqueue(c, sl.in.as<uint8_t>(), vi.data(), vi.size(), d, d + L.dig_off(), nullptr, d_mask, s)) return r;
+    TE_HIP(hipMemcpyAsync(sl.verh.u8() + L.h_mask_p(), d_mask, L.mask_b, hipMemcpyDeviceToHost, s));
+    if (!sl.peers) TE_HIP(hipEventCreateWithFlags(&sl.peers, hipEventDisableTiming | hipEventBlockingSync));
+    TE_HIP(hipEventRecord(sl.peers, s));
+    st.slices_hashed_device += vi.size();
+    return TE_OK;
+}
+
+// Stage A of a repair window: the plan's fragments, packed (each 16-byte aligned, as
+// te_slicer_repair places them); the repair kernels address them through helper_off.
+int repair_stage_a(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
+    const uint32_t n = (uint32_t)c->h.n;
+    RebuildPipe::Slot &sl = P.slot[k];
+    const hipStream_t s = read_slot_stream(c, k);
+    te_rebuild_launch_stats &st = c->rbs;
+    st.windows++;
+    st.objects += W.nobj;
+    W.frag_off.assign(W.nobj * n, ~0ull);
+    W.out_dev.resize(W.nobj);
+    W.out_len.resize(W.nobj);
+    W.out_host.resize(W.nobj);
+    W.lost.resize(W.nobj);
+    W.run.resize(W.nobj);
+    W.hout.clear();
+    std::vector<CopyRun> hin;
+    uint64_t in_sz = 0, need[64], max_len = 0, sum_len = 0;
+    bool dword = true;
+    W.out_sz = 0;
+    for (size_t o = 0; o < W.nobj; o++) {
+        const te_repair_plan *p = W.rep[o].plan;
+        plan_needs(p, need);
+        for (uint32_t b = 0; b < n; b++) {
+            if (!need[b]) continue;
+            W.frag_off[o * n + b] = in_sz;
+            const uint64_t host = W.rep[o].helper_off[b];
+            if (!hin.empty() && hin.back().host + hin.back().len == host && hin.back().dev + hin.back().len == in_sz)
+                hin.back().len += need[b];
+            else
+                hin.push_back({host, in_sz, need[b]});
+            in_sz += (need[b] + 15) & ~15ull;
+            st.pieces_uploaded++;
+            st.bytes_h2d += need[b];
+        }
+        W.run[o] = o;
+        W.lost[o] = p->lost;
+        W.out_len[o] = plan_out_bytes(p);
+        W.out_host[o] = W.rep[o].out_off;
+        W.out_dev[o] = W.out_sz;
+        if (!W.hout.empty() && W.hout.back().host + W.hout.back().len == W.out_host[o] &&
+            W.hout.back().dev + W.hout.back().len == W.out_sz)
+            W.hout.back().len += W.out_len[o];
+        else
+            W.hout.push_back({W.out_host[o], W.out_sz, W.out_len[o]});
+        W.out_sz += (W.out_len[o] + 15) & ~15ull;
+        max_len = std::max(max_len, W.out_len[o]);
+        sum_len += W.out_len[o];
+        dword = dword && W.out_len[o] % 4u == 0 && W.out_host[o] % 4u == 0;
+    }
+    W.device_hash = W.h_leaves && !W.copy_only && W.nobj && dword && !host_hash_wins(W.mode, W.nobj, max_len, sum_len);
+    W.resolved = true;
+    TE_HIP(sl.in.ensure(in_sz + 16));
+    if (int r = rebuild_upload(c, sl, W, hin, s)) return r;
+    if (W.device_hash) return rebuild_ver_begin(c, sl, W, s);
+    return TE_OK;
+}
+
+// Stage B (handle locked, its device current): the kernels, the rebuilt slices' hashes, the D2H copies.
+int rebuild_stage_b(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
+    const uint32_t n = (uint32_t)c->h.n;
+    RebuildPipe::Slot &sl = P.slot[k];
+    const hipStream_t s = read_slot_stream(c, k);
+    te_rebuild_launch_stats &st = c->rbs;
+    const VerLayout L = ver_layout(c, W);
+    if (!W.resolved) {  // recover, device hashing: the window's wait for its peers' masks
+        TE_HIP(hipEventSynchronize(sl.peers));
+        st.host_waits++;
+        memcpy(W.good.data(), sl.verh.u8() + L.h_mask_p(), W.nobj * sizeof(uint32_t));
+        recover_resolve(c, W);
+    }
+    if (!sl.done) TE_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
+    if (!W.run.empty()) {
+        TE_HIP(sl.out.ensure(W.out_sz + 16));
+        uint8_t *const d_in = sl.in.as<uint8_t>(), *const d_out = sl.out.as<uint8_t>();
+        if (W.copy_only) {
+        } else if (W.rep) {
+            std::vector<RepItem> items(W.nobj);
+            for (size_t o = 0; o < W.nobj; o++)
+                items[o] = RepItem{W.rep[o].plan, W.frag_off.data() + o * n, W.out_dev[o], W.rep[o].metadata};
+            if (int r = repair_enqueue(c, d_in, items.data(), items.size(), d_out, s)) return r;
+        } else {
+            std::vector<te_recover_object> objs;
+            std::vector<uint8_t> meta;
+            for (size_t o : W.run) {
+                objs.push_back(te_recover_object{W.in_base[o], W.rec[o].slice_len, W.good[o], W.rec[o].lost, W.out_dev[o]});
+                meta.insert(meta.end(), W.h_meta + o * TE_META_SIZE, W.h_meta + (o + 1) * TE_META_SIZE);
+            }
+            if (int r = recover_batch(c, &W.cfg, d_in, objs.data(), meta.data(), objs.size(), d_out, s, true, true)) return r;
+        }
+        if (W.device_hash) {
+            std::vector<te_verify_item> vi;
+            for (size_t o : W.run)
+                vi.push_back(te_verify_item{W.out_dev[o], W.out_len[o], (uint32_t)(o * n + W.lost[o]), (uint32_t)o, 1u, 0});
+            uint8_t *const d = sl.ver.as<uint8_t>();
+            uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + L.mask_o_off());
+            if (int r = verify_enqueue(c, d_out, vi.data(), vi.size(), d, d + L.dig_off() + L.dig_p, nullptr, d_mask, s)) return r;
+            TE_HIP(hipMemcpyAsync(sl.verh.u8() + L.h_mask_o(), d_mask, L.mask_b, hipMemcpyDeviceToHost, s));
+            st.slices_hashed_device += vi.size();
+        }
+        for (const CopyRun &r : W.hout) st.bytes_d2h += r.len;
+        if (W.pinned_out) {
+            if (int r = copy_runs(W.hout, d_out, W.h_out, hipMemcpyDeviceToHost, s)) return r;
+        } else {  // the device image as it is, into the slot's staging
+            TE_HIP(sl.hout.ensure(W.out_sz));
+            TE_HIP(hipMemcpyAsync(sl.hout.p, d_out, W.out_sz, hipMemcpyDeviceToHost, s));
+        }
+    }
+    TE_HIP(hipEventRecord(sl.done, s));
+    return TE_OK;
+}
+
+// Stage C (its device current): the window's results are on the host.
+int rebuild_stage_c(te_clay *c, RebuildPipe &P, int k, RebuildWin &W, bool last) {
+    RebuildPipe::Slot &sl = P.slot[k];
+    te_rebuild_launch_stats &st = c->rbs;
+    TE_HIP(hipEventSynchronize(sl.done));
+    if (W.run.empty()) return TE_OK;
+    const bool verified = W.h_leaves && !W.copy_only;
+    if (!last && (verified || !W.pinned_out)) st.host_waits++;
+    if (!W.pinned_out) {
+        std::vector<tec::CopyPool::Seg> segs;
+        for (const CopyRun &r : W.hout) segs.push_back({W.h_out + r.host, sl.hout.u8() + r.dev, (size_t)r.len});
+        copy_pool(c->device).run(segs);
+    }
+    if (!verified) return TE_OK;
+    if (W.device_hash) {
+        const VerLayout L = ver_layout(c, W);
+        const uint32_t *m = reinterpret_cast<const uint32_t *>(sl.verh.u8() + L.h_mask_o());
+        for (size_t o : W.run) W.h_ok[o] = m[o] & 1u;
+        return TE_OK;
+    }
+    const size_t n = (size_t)c->h.n;
+    std::vector<HashItem> items;
+    for (size_t o : W.run)
+        items.push_back({W.h_out + W.out_host[o], W.out_len[o], W.h_leaves + (o * n + W.lost[o]) * TE_HASH_SIZE});
+    std::vector<uint8_t> ok;
+    hash_items_host(items, c->device, ok);
+    for (size_t j = 0; j < W.run.size(); j++) W.h_ok[W.run[j]] = ok[j];
+    st.slices_hashed_host += items.size();
+    return TE_OK;
+}
+
+// The driver: handle locked, its device current, the windows filled in.
+int rebuild_run(te_clay *c, std::vector<RebuildWin> &wins) {
+    if (int r = read_streams(c)) return r;
+    if (!c->rbpipe) c->rbpipe = new RebuildPipe();
+    RebuildPipe &P = *c->rbpipe;
+    const size_t nw = wins.size();
+    int rc = TE_OK;
+    for (size_t w = 0; w < nw + 2 && !rc; w++) {
+        if (w < nw) rc = wins[w].rep ? repair_stage_a(c, P, (int)(w % RebuildPipe::R), wins[w])
+                                     : recover_stage_a(c, P, (int)(w % RebuildPipe::R), wins[w]);
+        if (!rc && w >= 1 && w - 1 < nw) rc = rebuild_stage_b(c, P, (int)((w - 1) % RebuildPipe::R), wins[w - 1]);
+        if (!rc && w >= 2) rc = rebuild_stage_c(c, P, (int)((w - 2) % RebuildPipe::R), wins[w - 2], w - 2 == nw - 1);
+    }
+    // also after a failure: copies from and to the caller's buffers may still be queued
+    const int r2 = read_drain(c);
+    for (auto &sl : P.slot)  // as the snapshot host calls: large window buffers are not kept
+        for (DevBuf *b : {&sl.in, &sl.out})
+            if (b->cap > ((size_t)256 << 20)) b->release();
+    return rc ? rc : r2;
+}
+
+bool rebuild_copy_only() {  // read per call: a benchmark switches it between legs
+    const char *co = tec_knob("TEC_REBUILD_COPY_ONLY");
+    return co && co[0] == '1';
+}
+
+}  // namespace
+
+extern "C" {
+
+int te_repair_window_plan(const te_clay *c, const te_repair_object *objs, size_t nobj, size_t window_bytes,
+                          size_t *cuts, size_t cap, size_t *nwindows) {
+    if (!c || !nwindows || (!objs && nobj)) return TE_ERR_INVALID_ARG;
+    *nwindows = 0;
+    std::vector<uint64_t> bytes;
+    if (int r = repair_object_bytes(c, objs, nobj, bytes)) return r;
+    std::vector<size_t> v;
+    rebuild_cuts(bytes, window_bytes, v);
+    return cuts_out(v, cuts, cap, nwindows);
+}
+
+int te_recover_window_plan(const te_clay *c, const te_recover_object *objs, size_t nobj, size_t window_bytes,
+                           size_t *cuts, size_t cap, size_t *nwindows) {
+    if (!c || !nwindows || (!objs && nobj)) return TE_ERR_INVALID_ARG;
+    *nwindows = 0;
+    std::vector<uint64_t> bytes;
+    recover_object_bytes(c, objs, nobj, bytes);
+    std::vector<size_t> v;
+    rebuild_cuts(bytes, window_bytes, v);
+    return cuts_out(v, cuts, cap, nwindows);
+}
+
+int te_repair_batch_host(te_clay *c, const uint8_t *h_helpers, const te_repair_object *objs, const uint8_t *h_leaves,
+                         size_t nobj, uint8_t *h_out, uint32_t *h_ok, size_t window_bytes) {
+    if (!c || ((!objs || !h_helpers || !h_out) && nobj) || (h_leaves && !h_ok && nobj)) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n;
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    uint64_t need[64];
+    for (size_t i = 0; i < nobj; i++) {
+        const te_repair_plan *p = objs[i].plan;
+        if (!p || p->n != n || p->d != (uint32_t)c->h.d || p->n > 64 || p->lost >= n) return TE_ERR_INVALID_ARG;
+        plan_needs(p, need);
+        for (uint32_t sl = 0; sl < n; sl++)
+            if (need[sl] && objs[i].helper_off[sl] == ~0ull) return TE_ERR_MISSING_HELPER;
+    }
+    std::vector<uint64_t> bytes;
+    if (int r = repair_object_bytes(c, objs, nobj, bytes)) return r;
+    std::vector<size_t> cuts;
+    rebuild_cuts(bytes, window_bytes, cuts);
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->rls = te_repair_launch_stats{};
+    c->rbs = te_rebuild_launch_stats{};
+    if (nobj == 0) return TE_OK;
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    const bool pin_in = host_pinned(h_helpers), pin_out = host_pinned(h_out), copy_only = rebuild_copy_only();
+    std::vector<RebuildWin> wins(cuts.size() - 1);
+    for (size_t w = 0; w < wins.size(); w++) {
+        RebuildWin &W = wins[w];
+        const size_t a = cuts[w];
+        W.rep = objs + a;
+        W.h_in = h_helpers;
+        W.h_out = h_out;
+        W.h_leaves = h_leaves ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
+        W.nobj = cuts[w + 1] - a;
+        W.h_ok = h_ok ? h_ok + a : nullptr;
+        W.mode = g_commit_hashing.load();
+        W.pinned_in = pin_in;
+        W.pinned_out = pin_out;
+        W.copy_only = copy_only;
+    }
+    return rebuild_run(c, wins);
+}
+
+int te_recover_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_recover_object *objs,
+                          const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *h_out,
+                          uint32_t *h_rejected_mask, uint32_t *h_ok, int *h_status, size_t window_bytes) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_slices || !h_out) && nobj)) return TE_ERR_INVALID_ARG;
+    const bool verified = h_leaves != nullptr;
+    if (verified && (!h_status || !h_ok) && nobj) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n;
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    std::vector<int> pre(nobj, TE_OK);
+    for (size_t i = 0; i < nobj; i++) {
+        if (objs[i].lost >= n) return TE_ERR_INVALID_SLICE;
+        DecItem it{};
+        const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, it);
+        if (r && !(verified && r == TE_ERR_NOT_ENOUGH_SLICES)) return r;
+        pre[i] = r;
+        if (r) continue;
+        te_geometry g;
+        te_slicer_geometry(c, it.blob_len, &g);
+        if (g.slice_len != objs[i].slice_len) return TE_ERR_INVALID_LAYOUT;
+    }
+    std::vector<uint64_t> bytes;
+    recover_object_bytes(c, objs, nobj, bytes);
+    std::vector<size_t> cuts;
+    rebuild_cuts(bytes, window_bytes, cuts);
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->els = te_encode_launch_stats{};
+    c->rbs = te_rebuild_launch_stats{};
+    if (nobj == 0) return TE_OK;
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    // h_slices is of one kind (header): asked of the first present slice, absent slots may be unmapped
+    bool pin_in = true;
+    for (size_t i = 0; i < nobj; i++)
+        if (const uint32_t m = objs[i].avail_mask & slice_bits(c)) {
+            pin_in = host_pinned(h_slices + objs[i].slices_off + (uint64_t)__builtin_ctz(m) * objs[i].slice_len);
+            break;
+        }
+    const bool pin_out = host_pinned(h_out), copy_only = rebuild_copy_only();
+    std::vector<RebuildWin> wins(cuts.size() - 1);
+    for (size_t w = 0; w < wins.size(); w++) {
+        RebuildWin &W = wins[w];
+        const size_t a = cuts[w];
+        W.rec = objs + a;
+        W.cfg = *cfg;
+        W.h_in = h_slices;
+        W.h_out = h_out;
+        W.h_meta = h_meta + a * TE_META_SIZE;
+        W.h_leaves = verified ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
+        W.nobj = cuts[w + 1] - a;
+        W.h_rej = h_rejected_mask ? h_rejected_mask + a : nullptr;
+        W.h_ok = h_ok ? h_ok + a : nullptr;
+        W.h_status = h_status ? h_status + a : nullptr;
+        W.pre = pre.data() + a;
+        W.mode = g_commit_hashing.load();
+        W.pinned_in = pin_in;
+        W.pinned_out = pin_out;
+        W.copy_only = copy_only;
+    }
+    return rebuild_run(c, wins);
+}
+
+int te_clay_rebuild_launch_stats(te_clay *c, te_rebuild_launch_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->rbs;
+    return TE_OK;
 }
 
 }  // extern "C"
