@@ -29,6 +29,7 @@
 #include "rs16.hpp"
 #include "host_hash.hpp"
 #include "copy_pool.hpp"
+#include "win_plan.hpp"
 #include "dec_class.hpp"
 
 using namespace tec;
@@ -431,12 +432,10 @@ uint64_t get_u64(const uint8_t *p) {
 
 bool valid_stripe(uint64_t s) { return s == kStripeSizes[0] || s == kStripeSizes[1] || s == kStripeSizes[2]; }
 
-// the host read pipeline's per-handle buffers (te_decode_batch_host, below)
-struct ReadPipe;
-void read_pipe_free(ReadPipe *p);
-// and the host rebuild pipeline's (te_repair_batch_host / te_recover_batch_host)
-struct RebuildPipe;
-void rebuild_pipe_free(RebuildPipe *p);
+// the host read and rebuild pipelines' per-handle window buffers (te_decode_batch_host,
+// te_repair_batch_host / te_recover_batch_host, below)
+struct WinPipe;
+void win_pipe_free(WinPipe *p);
 
 }  // namespace
 
@@ -554,10 +553,10 @@ struct te_clay {
     te_repair_launch_stats rls{};
     // te_decode_batch_host / te_decode_verified_batch_host: their window buffers (kept between
     // calls, as the encode pipeline's are) and the last call's te_read_launch_stats
-    ReadPipe *rpipe = nullptr;
+    WinPipe *rpipe = nullptr;
     te_read_launch_stats rds{};
     // te_repair_batch_host / te_recover_batch_host: the same
-    RebuildPipe *rbpipe = nullptr;
+    WinPipe *rbpipe = nullptr;
     te_rebuild_launch_stats rbs{};
     // te_snapshot_*: the decode's descriptor arena (payload offsets, segment capacities), its
     // page-locked header read-back, the host forms' device buffers (kept between calls) and the last
@@ -582,9 +581,9 @@ static void release_device_state(te_clay *c) {
     if (c->cls_fork) (void)hipEventDestroy(c->cls_fork), c->cls_fork = nullptr;
     for (hipEvent_t &pe : c->cls_join)
         if (pe) (void)hipEventDestroy(pe), pe = nullptr;
-    read_pipe_free(c->rpipe);
+    win_pipe_free(c->rpipe);
     c->rpipe = nullptr;
-    rebuild_pipe_free(c->rbpipe);
+    win_pipe_free(c->rbpipe);
     c->rbpipe = nullptr;
     c->enc.release();
     c->dec.release();
@@ -2204,21 +2203,11 @@ struct CommitOut {
     uint32_t height;
 };
 
-// Host <-> device copy runs of a window: consecutive objects contiguous on the host move with one DMA.
-struct CopyRun { uint64_t host, dev, len; };
-
 // Device layout of objects [a, b) placed from offsets (din, dout) of a slot's buffers: the encode
 // descriptors (`local`, offsets relative to the buffers) and the H2D / D2H copy runs.
 static void window_layout(const te_object *objs, const std::vector<uint64_t> &out_bytes, size_t a, size_t b,
                           uint64_t din, uint64_t dout, std::vector<te_object> &local, std::vector<CopyRun> &hin,
                           std::vector<CopyRun> &hout) {
-    auto add_run = [](std::vector<CopyRun> &v, uint64_t host, uint64_t dev, uint64_t len) {
-        if (!len) return;
-        if (!v.empty() && v.back().host + v.back().len == host && v.back().dev + v.back().len == dev)
-            v.back().len += len;
-        else
-            v.push_back({host, dev, len});
-    };
     local.clear();
     hin.clear();
     hout.clear();
@@ -2226,7 +2215,7 @@ static void window_layout(const te_object *objs, const std::vector<uint64_t> &ou
         local.push_back(te_object{din, objs[o].blob_len, dout, objs[o].chunk_index});
         add_run(hin, objs[o].data_off, din, objs[o].blob_len);
         add_run(hout, objs[o].out_off, dout, out_bytes[o]);
-        din += (objs[o].blob_len + 15) & ~15ull;  // device copies 16-byte aligned
+        din += align16(objs[o].blob_len);  // device copies 16-byte aligned
         dout += out_bytes[o];
     }
 }
@@ -2277,7 +2266,7 @@ static int encode_host_impl(te_clay *c, const te_slicer_cfg *cfg, const uint8_t 
         size_t j = i;
         uint64_t in_sz = 0, out_sz = 0;
         while (j < nobj && (j == i || in_sz + out_sz + objs[j].blob_len + out_bytes[j] <= window_bytes)) {
-            in_sz += (objs[j].blob_len + 15) & ~15ull;  // device copies 16-byte aligned
+            in_sz += align16(objs[j].blob_len);  // device copies 16-byte aligned
             out_sz += out_bytes[j];
             j++;
         }
@@ -2361,7 +2350,7 @@ struct CommitBatch {
     uint32_t n = 0;
     std::vector<uint64_t> out_bytes, slice_len;
     uint64_t leaf_b = 0, proof_b = 0;
-    uint64_t in_bytes(size_t o) const { return (objs[o].blob_len + 15) & ~15ull; }  // device copies 16-byte aligned
+    uint64_t in_bytes(size_t o) const { return align16(objs[o].blob_len); }  // device copies 16-byte aligned
 };
 
 static int commit_prepare(const te_clay *c, CommitBatch &B) {
@@ -3702,7 +3691,7 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
     for (size_t i = 0; i < nobj;) {
         Win w{i, i, 0, 0};
         while (w.e < nobj) {
-            const uint64_t bb = (items[w.e].blob_len + 15) & ~15ull, sb = (uint64_t)n * objs[w.e].slice_len;
+            const uint64_t bb = align16(items[w.e].blob_len), sb = (uint64_t)n * objs[w.e].slice_len;
             if (w.e > w.b && (w.blob + bb > kWinBlob || w.slices + sb > kWinSlices)) break;
             w.blob += bb;
             w.slices += sb;
@@ -3743,7 +3732,7 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
             e.data_off = bo;
             e.out_off = so;
             wenc.push_back(e);
-            bo += (items[i].blob_len + 15) & ~15ull;
+            bo += align16(items[i].blob_len);
             so += (uint64_t)n * objs[i].slice_len;
         }
         if ((r = decode_enqueue(c, cfg, d_slices, items.data() + w.b, w.e - w.b, blob, s, false))) break;
@@ -4276,7 +4265,7 @@ int te_slicer_repair(te_clay *c, const te_repair_plan *p, const uint8_t *const *
         if (!need[sl]) continue;
         if (!helper_data[sl] || helper_lens[sl] < need[sl]) return TE_ERR_MISSING_HELPER;
         off[sl] = total;
-        total += (need[sl] + 15) & ~15ull;
+        total += align16(need[sl]);
     }
     std::lock_guard<std::mutex> lk(c->mu);
     c->rls = te_repair_launch_stats{};
@@ -4550,6 +4539,28 @@ int verify_enqueue(te_clay *c, const uint8_t *d_data, const te_verify_item *item
     return A.mark_done(s);
 }
 
+// Device hashing in a verify workspace (the handle's or a window slot's) of layout L: the expected
+// leaves on the device and every mask array zeroed ...
+int ver_begin(DevBuf &ver, HostBuf &verh, const VerLayout &L, const uint8_t *h_leaves, hipStream_t s) {
+    TE_HIP(ver.ensure(L.total()));
+    TE_HIP(verh.ensure(L.h_total()));
+    memcpy(verh.p, h_leaves, L.exp_b);
+    TE_HIP(hipMemcpyAsync(ver.p, verh.p, L.exp_b, hipMemcpyHostToDevice, s));
+    TE_HIP(hipMemsetAsync(ver.as<uint8_t>() + L.mask_off(0), 0, L.narr * L.mask_b, s));
+    return TE_OK;
+}
+
+// ... then `items` of d_data hashed into mask array `which` (0: peers, 1: rebuilt slices) and that
+// array's D2H copy to the workspace's host side.
+int ver_masks(te_clay *c, DevBuf &ver, HostBuf &verh, const uint8_t *d_data, const std::vector<te_verify_item> &items,
+              const VerLayout &L, int which, hipStream_t s) {
+    uint8_t *const d = ver.as<uint8_t>();
+    uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + L.mask_off(which));
+    if (int r = verify_enqueue(c, d_data, items.data(), items.size(), d, d + L.dig_off(which), nullptr, d_mask, s)) return r;
+    TE_HIP(hipMemcpyAsync(verh.u8() + L.h_mask(which), d_mask, L.mask_b, hipMemcpyDeviceToHost, s));
+    return TE_OK;
+}
+
 // Handle locked, its device current.  Verify `items` (their `expected` index h_expected's nexp
 // hashes, their `object` one of nmask masks) in the handle's workspace and WAIT for the masks:
 // h_good[o] = the bits of object o's matching items.
@@ -4557,19 +4568,12 @@ int verify_wait(te_clay *c, const uint8_t *d_data, const std::vector<te_verify_i
                 size_t nexp, size_t nmask, uint32_t *h_good, hipStream_t s) {
     for (size_t o = 0; o < nmask; o++) h_good[o] = 0;
     if (items.empty()) return TE_OK;
-    const size_t exp_b = nexp * TE_HASH_SIZE, dig_b = items.size() * TE_HASH_SIZE, mask_b = nmask * sizeof(uint32_t);
-    TE_HIP(c->ver_buf.ensure(exp_b + dig_b + mask_b));
-    TE_HIP(c->ver_host.ensure(exp_b + mask_b));
-    uint8_t *const d = c->ver_buf.as<uint8_t>();
-    uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + exp_b + dig_b);
-    memcpy(c->ver_host.p, h_expected, exp_b);
-    TE_HIP(hipMemcpyAsync(d, c->ver_host.p, exp_b, hipMemcpyHostToDevice, s));
-    TE_HIP(hipMemsetAsync(d_mask, 0, mask_b, s));
-    int r = verify_enqueue(c, d_data, items.data(), items.size(), d, d + exp_b, nullptr, d_mask, s);
+    const VerLayout L{nexp * TE_HASH_SIZE, items.size() * TE_HASH_SIZE, 0, nmask * sizeof(uint32_t), 1};
+    int r = ver_begin(c->ver_buf, c->ver_host, L, h_expected, s);
+    if (!r) r = ver_masks(c, c->ver_buf, c->ver_host, d_data, items, L, 0, s);
+    if (!r) r = sync_sleep(s);
     if (r) return r;
-    TE_HIP(hipMemcpyAsync(c->ver_host.u8() + exp_b, d_mask, mask_b, hipMemcpyDeviceToHost, s));
-    if ((r = sync_sleep(s))) return r;
-    memcpy(h_good, c->ver_host.u8() + exp_b, mask_b);
+    memcpy(h_good, c->ver_host.u8() + L.h_mask(0), L.mask_b);
     return TE_OK;
 }
 
@@ -4582,6 +4586,21 @@ void verify_push_slices(std::vector<te_verify_item> &vi, size_t obj, uint32_t n,
         if ((avail >> b) & 1u)
             vi.push_back(te_verify_item{slices_off + (uint64_t)b * slice_len, slice_len, (uint32_t)(obj * n + b),
                                         (uint32_t)obj, 1u << b, 0});
+}
+
+// One object's survivor set once its slices are hashed: ok = the present slices (`avail`) that
+// matched (`good`), the others into *rej; an object that passed on its present slices (`pre`, the
+// caller's validation before anything was enqueued) is validated again on ok, and that is its
+// *status.  Returns the status; with TE_OK, `it` is the object's decode item and ok what it reads.
+int resolve_survivors(const te_clay *c, uint32_t avail, uint64_t slice_len, const uint8_t *meta, int pre, uint32_t good,
+                      uint32_t *rej, int *status, uint32_t &ok, DecItem &it) {
+    ok = avail & good;
+    if (rej) *rej = avail & ~ok;
+    int st = pre;
+    if (!st) st = decode_validate(c, meta, slice_len, ok, it);
+    if (status) *status = st;
+    if (st) ok = 0;
+    return st;
 }
 
 }  // namespace
@@ -4631,6 +4650,8 @@ int decode_verified_locked(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     std::vector<te_verify_item> vi;
     for (size_t i = 0; i < nobj; i++) {
         // an object with too few slices to begin with is that object's outcome, not the call's
+        // (the device entry points validate on the caller's unmasked avail_mask, the host pipelines
+        // on avail_mask & all)
         const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, items[i]);
         if (r && r != TE_ERR_NOT_ENOUGH_SLICES) return r;
         h_status[i] = r;
@@ -4641,11 +4662,11 @@ int decode_verified_locked(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     if (r) return r;
     std::vector<DecItem> run;
     for (size_t i = 0; i < nobj; i++) {
-        const uint32_t avail = objs[i].avail_mask & all, ok = avail & good[i];
-        if (h_rejected_mask) h_rejected_mask[i] = avail & ~ok;
-        if (h_status[i]) continue;
+        uint32_t ok;
         DecItem it{};
-        if ((h_status[i] = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, ok, it))) continue;
+        if (resolve_survivors(c, objs[i].avail_mask & all, objs[i].slice_len, h_meta + i * TE_META_SIZE, h_status[i], good[i],
+                              h_rejected_mask ? h_rejected_mask + i : nullptr, h_status + i, ok, it))
+            continue;
         it.in_base = objs[i].slices_off;
         it.out_off = objs[i].out_off;
         run.push_back(it);
@@ -4688,6 +4709,7 @@ int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const
     std::vector<te_verify_item> vi;
     for (size_t i = 0; i < nobj; i++) {
         DecItem it{};
+        // on the caller's unmasked avail_mask, as te_decode_verified_batch_device
         const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, it);
         if (r && r != TE_ERR_NOT_ENOUGH_SLICES) return r;
         h_status[i] = r;
@@ -4708,11 +4730,11 @@ int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const
     std::vector<uint8_t> run_meta;
     std::vector<size_t> run_of;
     for (size_t i = 0; i < nobj; i++) {
-        const uint32_t avail = objs[i].avail_mask & all, ok = avail & good[i];
-        if (h_rejected_mask) h_rejected_mask[i] = avail & ~ok;
-        if (h_status[i]) continue;
+        uint32_t ok;
         DecItem it{};
-        if ((h_status[i] = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, ok, it))) continue;
+        if (resolve_survivors(c, objs[i].avail_mask & all, objs[i].slice_len, h_meta + i * TE_META_SIZE, h_status[i], good[i],
+                              h_rejected_mask ? h_rejected_mask + i : nullptr, h_status + i, ok, it))
+            continue;
         te_recover_object o = objs[i];
         o.avail_mask = ok;
         run.push_back(o);
@@ -4848,27 +4870,34 @@ int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_
 //      D2H copies of their blob_len bytes.
 // The driver runs A(w+1) before B(w): B(w)'s wait is spent with the next window's upload queued
 // behind this window's, and the copy engines, the kernels and the host pool overlap across slots.
+// The rebuild pipeline (below) runs on the same pieces, each written once: window_cuts, add_run,
+// align16 and VerLayout (win_plan.hpp), the slots (WinPipe), the pool's hashing (hash_items_host),
+// the verify workspace (ver_begin, ver_masks), an object's survivor set (resolve_survivors) and
+// stage A of a window of peer slices (peer_stage_a: a read's and a recover's).
 // ------------------------------------------------------------------------------------------
 namespace {
 
-struct ReadPipe {
+// A pipeline's window slots.  The handle's read pipeline, its rebuild pipeline and every stream
+// reader hold an instance of their own (what persists between calls is each one's).
+struct WinPipe {
     static constexpr int R = te_clay::kPipe;
     struct Slot {
-        DevBuf in, out;   // the window's slices (n * slice_len per object) and decoded objects
-        DevBuf ver;       // device hashing: expected leaves | digests | good masks
-        HostBuf verh;     // its page-locked host side: expected leaves | good masks
-        hipEvent_t verified = nullptr;  // after the masks' D2H copy
+        DevBuf in, out;     // the window's slices / fragments and its decoded objects / rebuilt slices
+        DevBuf ver;         // device hashing: the verify workspace (VerLayout)
+        HostBuf verh;       // its page-locked host side
+        HostBuf hin, hout;  // rebuild: page-locked staging of pageable caller buffers
+        hipEvent_t peers = nullptr;  // after the peer masks' D2H copy
+        hipEvent_t done = nullptr;   // rebuild: after the window's last D2H copy
     } slot[R];
 };
 
-void read_pipe_free(ReadPipe *p) {  // its streams drained, its device current
+void win_pipe_free(WinPipe *p) {  // its streams drained, its device current
     if (!p) return;
     for (auto &sl : p->slot) {
-        sl.in.release();
-        sl.out.release();
-        sl.ver.release();
-        sl.verh.release();
-        if (sl.verified) (void)hipEventDestroy(sl.verified);
+        for (DevBuf *b : {&sl.in, &sl.out, &sl.ver}) b->release();
+        for (HostBuf *b : {&sl.verh, &sl.hin, &sl.hout}) b->release();
+        if (sl.peers) (void)hipEventDestroy(sl.peers);
+        if (sl.done) (void)hipEventDestroy(sl.done);
     }
     delete p;
 }
@@ -4895,6 +4924,7 @@ struct ReadWin {
     std::vector<DecItem> run;       // the objects that decode; out_off = their place in the slot's output
     std::vector<CopyRun> hout;
     uint64_t out_sz = 0;
+    VerLayout vl{};                 // device hashing: the slot's verify workspace
 };
 
 // Every object checked like Slicer::decode on its present slices (nothing is enqueued before this
@@ -4912,24 +4942,26 @@ int read_validate(const te_clay *c, const te_decode_object *objs, const uint8_t 
     return TE_OK;
 }
 
-// te_decode_window_plan: at least one object per window, then as many as fit.
+// te_decode_window_plan: an object counts its present slices and its decoded bytes.
 int read_cuts(const te_clay *c, const te_decode_object *objs, const uint8_t *h_meta, size_t nobj, size_t window_bytes,
               std::vector<size_t> &cuts) {
-    if (window_bytes == 0) window_bytes = (size_t)128 << 20;
     const uint32_t all = slice_bits(c);
-    cuts.assign(1, 0);
-    uint64_t sum = 0;
+    std::vector<uint64_t> bytes(nobj);
     for (size_t i = 0; i < nobj; i++) {
         te_slice_metadata m;
         if (int r = te_slice_metadata_from_slice(h_meta + i * TE_META_SIZE, TE_META_SIZE, &m)) return r;
-        const uint64_t b = (uint64_t)__builtin_popcount(objs[i].avail_mask & all) * objs[i].slice_len + m.blob_len;
-        if (i > cuts.back() && sum + b > window_bytes) {
-            cuts.push_back(i);
-            sum = 0;
-        }
-        sum += b;
+        bytes[i] = (uint64_t)__builtin_popcount(objs[i].avail_mask & all) * objs[i].slice_len + m.blob_len;
     }
-    if (nobj) cuts.push_back(nobj);
+    window_cuts(bytes, window_bytes, cuts);
+    return TE_OK;
+}
+
+// A window plan out through the C ABI (te_*_window_plan).
+int cuts_out(const std::vector<size_t> &v, size_t *cuts, size_t cap, size_t *nwindows) {
+    *nwindows = v.size() - 1;
+    if (!cuts) return TE_OK;
+    if (cap < v.size()) return TE_ERR_BUFFER_TOO_SMALL;
+    memcpy(cuts, v.data(), v.size() * sizeof(size_t));
     return TE_OK;
 }
 
@@ -4942,18 +4974,11 @@ int read_streams(te_clay *c) {  // handle locked, its device current
     return TE_OK;
 }
 
-// hash_leaf of the window's present slices on the host pool, from the caller's buffer:
-// good[o] = the present slices of object o that match their leaf.  Waits for the pool.
-void read_hash_host(const ReadWin &W, uint32_t n, uint32_t all, int device, std::vector<uint32_t> &good,
-                    te_read_launch_stats &st) {
-    struct Item { const uint8_t *p; uint64_t len; uint32_t obj, bit; };
-    std::vector<Item> items;
-    for (size_t o = 0; o < W.nobj; o++)
-        for (uint32_t b = 0; b < n; b++)
-            if (((W.objs[o].avail_mask & all) >> b) & 1u)
-                items.push_back({W.h_slices + W.objs[o].slices_off + (uint64_t)b * W.objs[o].slice_len,
-                                 W.objs[o].slice_len, (uint32_t)o, b});
-    good.assign(W.nobj, 0);
+struct HashItem { const uint8_t *p; uint64_t len; const uint8_t *expect; };
+
+// hash_leaf of the items on the host pool against their expected hashes; waits for the pool.
+void hash_items_host(const std::vector<HashItem> &items, int device, std::vector<uint8_t> &okv) {
+    okv.assign(items.size(), 0);
     if (items.empty()) return;
     hh::Pool &pool = hh::Pool::get();
     // interleaved lanes raise one thread's rate, but a window of a few long slices (a 64 MiB
@@ -4962,12 +4987,11 @@ void read_hash_host(const ReadWin &W, uint32_t n, uint32_t all, int device, std:
     auto ok = std::make_shared<std::vector<uint8_t>>(items.size(), 0);
     auto job = std::make_shared<hh::Job>();
     std::vector<std::function<void()>> tasks;
-    const uint8_t *leaves = W.h_leaves;
     for (size_t j0 = 0; j0 < items.size();) {
         size_t j1 = j0 + 1;  // a task's lanes hash messages of one length
         while (j1 < items.size() && j1 - j0 < (size_t)lanes && items[j1].len == items[j0].len) j1++;
-        std::vector<Item> part(items.begin() + (ptrdiff_t)j0, items.begin() + (ptrdiff_t)j1);
-        tasks.push_back([part, j0, ok, job, leaves, n] {
+        std::vector<HashItem> part(items.begin() + (ptrdiff_t)j0, items.begin() + (ptrdiff_t)j1);
+        tasks.push_back([part, j0, ok, job] {
             const int L = (int)part.size();
             uint8_t dig[hh::kMaxLanes][TE_HASH_SIZE];
             const uint8_t *src[hh::kMaxLanes];
@@ -4977,10 +5001,7 @@ void read_hash_host(const ReadWin &W, uint32_t n, uint32_t all, int device, std:
                 dst[l] = dig[l];
             }
             hh::hash_leaves(L, src, part[0].len, dst);
-            for (int l = 0; l < L; l++) {
-                const Item &t = part[(size_t)l];
-                (*ok)[j0 + (size_t)l] = memcmp(dig[l], leaves + ((size_t)t.obj * n + t.bit) * TE_HASH_SIZE, TE_HASH_SIZE) == 0;
-            }
+            for (int l = 0; l < L; l++) (*ok)[j0 + (size_t)l] = memcmp(dig[l], part[(size_t)l].expect, TE_HASH_SIZE) == 0;
             job->done();
         });
         j0 = j1;
@@ -4988,9 +5009,7 @@ void read_hash_host(const ReadWin &W, uint32_t n, uint32_t all, int device, std:
     job->add((int64_t)tasks.size());
     pool.submit_after(nullptr, device, std::move(tasks));
     (void)job->wait();
-    for (size_t j = 0; j < items.size(); j++)
-        if ((*ok)[j]) good[items[j].obj] |= 1u << items[j].bit;
-    st.slices_hashed_host += items.size();
+    okv = *ok;
 }
 
 // The survivor sets are known: masks and statuses out, the objects that decode and their place in
@@ -5001,113 +5020,116 @@ void read_resolve(const te_clay *c, ReadWin &W) {
     W.hout.clear();
     W.out_sz = 0;
     for (size_t o = 0; o < W.nobj; o++) {
-        const uint32_t avail = W.objs[o].avail_mask & all, ok = avail & W.good[o];
-        if (W.h_leaves && W.h_rej) W.h_rej[o] = avail & ~ok;
-        int st = W.pre ? W.pre[o] : TE_OK;
         DecItem it{};
-        if (!st) st = decode_validate(c, W.h_meta + o * TE_META_SIZE, W.objs[o].slice_len, ok, it);
-        if (W.h_status) W.h_status[o] = st;
-        W.good[o] = st ? 0u : ok;  // the slices the decode reads from
+        // h_rej is written only when leaves were given; W.good becomes what the decode reads from
+        const int st = resolve_survivors(c, W.objs[o].avail_mask & all, W.objs[o].slice_len, W.h_meta + o * TE_META_SIZE,
+                                         W.pre ? W.pre[o] : TE_OK, W.good[o], W.h_leaves && W.h_rej ? W.h_rej + o : nullptr,
+                                         W.h_status ? W.h_status + o : nullptr, W.good[o], it);
         if (st) continue;
         it.in_base = W.in_base[o];
         it.out_off = W.out_sz;
         W.run.push_back(it);
-        if (it.blob_len) {
-            if (!W.hout.empty() && W.hout.back().host + W.hout.back().len == W.objs[o].out_off &&
-                W.hout.back().dev + W.hout.back().len == W.out_sz)
-                W.hout.back().len += it.blob_len;
-            else
-                W.hout.push_back({W.objs[o].out_off, W.out_sz, it.blob_len});
-        }
-        W.out_sz += (it.blob_len + 15) & ~15ull;  // device copies 16-byte aligned
+        add_run(W.hout, W.objs[o].out_off, W.out_sz, it.blob_len);
+        W.out_sz += align16(it.blob_len);
     }
     W.resolved = true;
 }
 
-// Stage A of a window on slot k (handle locked, its device current).
-int read_stage_a(te_clay *c, ReadPipe &P, int k, ReadWin &W) {
+// Stage A of a peer window -- a read's or a recover's -- on a slot and its stream (handle locked,
+// its device current).  `objs` are te_decode_object or te_recover_object, by the fields they share
+// (slices_off, slice_len, avail_mask), their slices in h_in.  The caller gives what differs:
+// `dword`, its own conditions for device hashing besides slice_len % 4; `results`, that the window
+// goes on to verify one rebuilt slice per object in the same workspace; the stats and their upload
+// counter; `resolve`, run once W.good holds the final survivor sets; `upload`, the H2D copy runs.
+template <class Win, class Obj, class Stats, class Resolve, class Upload>
+int peer_stage_a(te_clay *c, WinPipe::Slot &sl, hipStream_t s, Win &W, const Obj *objs, const uint8_t *h_in, bool dword,
+                 bool results, Stats &st, uint64_t Stats::*uploaded, Resolve resolve, Upload upload) {
     const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
-    ReadPipe::Slot &sl = P.slot[k];
-    const hipStream_t s = read_slot_stream(c, k);
-    te_read_launch_stats &st = c->rds;
     st.windows++;
     st.objects += W.nobj;
     W.in_base.resize(W.nobj);
     W.good.assign(W.nobj, 0);
     uint64_t in_sz = 0, max_slice = 0, slice_bytes = 0, nslices = 0;
-    bool dword = true;
     for (size_t o = 0; o < W.nobj; o++) {
         W.in_base[o] = in_sz;
-        in_sz += ((uint64_t)n * W.objs[o].slice_len + 15) & ~15ull;
-        const uint64_t np = (uint64_t)__builtin_popcount(W.objs[o].avail_mask & all);
+        in_sz += align16((uint64_t)n * objs[o].slice_len);
+        const uint64_t np = (uint64_t)__builtin_popcount(objs[o].avail_mask & all);
         nslices += np;
-        slice_bytes += np * W.objs[o].slice_len;
-        if (np) max_slice = std::max<uint64_t>(max_slice, W.objs[o].slice_len);
-        dword = dword && W.objs[o].slice_len % 4u == 0;
+        slice_bytes += np * objs[o].slice_len;
+        if (np) max_slice = std::max<uint64_t>(max_slice, objs[o].slice_len);
+        dword = dword && objs[o].slice_len % 4u == 0;
     }
-    W.device_hash = W.h_leaves && nslices && dword && !host_hash_wins(W.mode, nslices, max_slice, slice_bytes);
-    if (W.copy_only) W.device_hash = false;
-    if (!W.h_leaves || W.copy_only) {
-        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.objs[o].avail_mask & all;
-        read_resolve(c, W);
-    } else if (!W.device_hash) {
-        read_hash_host(W, n, all, c->device, W.good, st);
-        read_resolve(c, W);
-    } else {
-        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.objs[o].avail_mask & all;  // every present slice goes up
+    const bool verified = W.h_leaves && !W.copy_only;
+    W.device_hash = verified && nslices && dword && !host_hash_wins(W.mode, nslices, max_slice, slice_bytes);
+    if (verified && !W.device_hash) {  // the pool hashes the present slices where they lie
+        std::vector<HashItem> items;
+        std::vector<std::pair<uint32_t, uint32_t>> who;
+        for (size_t o = 0; o < W.nobj; o++)
+            for (uint32_t b = 0; b < n; b++)
+                if (((objs[o].avail_mask & all) >> b) & 1u) {
+                    items.push_back({h_in + objs[o].slices_off + (uint64_t)b * objs[o].slice_len, objs[o].slice_len,
+                                     W.h_leaves + (o * n + b) * TE_HASH_SIZE});
+                    who.push_back({(uint32_t)o, b});
+                }
+        std::vector<uint8_t> ok;
+        hash_items_host(items, c->device, ok);
+        for (size_t j = 0; j < items.size(); j++)
+            if (ok[j]) W.good[who[j].first] |= 1u << who[j].second;
+        st.slices_hashed_host += items.size();
+    } else {  // unverified: the present slices; device hashing: every present slice goes up
+        for (size_t o = 0; o < W.nobj; o++) W.good[o] = objs[o].avail_mask & all;
     }
+    if (!W.device_hash) resolve();
     TE_HIP(sl.in.ensure(in_sz + 16));
-    uint8_t *const d_in = sl.in.as<uint8_t>();
     std::vector<CopyRun> hin;
     std::vector<te_verify_item> vi;
     for (size_t o = 0; o < W.nobj; o++) {
-        const uint64_t len = W.objs[o].slice_len;
+        const uint64_t len = objs[o].slice_len;
         for (uint32_t b = 0; b < n; b++) {
             if (!((W.good[o] >> b) & 1u) || !len) continue;
-            const uint64_t host = W.objs[o].slices_off + (uint64_t)b * len, dev = W.in_base[o] + (uint64_t)b * len;
-            if (!hin.empty() && hin.back().host + hin.back().len == host && hin.back().dev + hin.back().len == dev)
-                hin.back().len += len;
-            else
-                hin.push_back({host, dev, len});
-            st.slices_uploaded++;
+            add_run(hin, objs[o].slices_off + (uint64_t)b * len, W.in_base[o] + (uint64_t)b * len, len);
+            (st.*uploaded)++;
             st.bytes_h2d += len;
         }
         if (W.device_hash) verify_push_slices(vi, o, n, W.in_base[o], len, W.good[o]);
     }
-    if (int r = copy_runs(hin, d_in, W.h_slices, hipMemcpyHostToDevice, s)) return r;
+    if (int r = upload(hin)) return r;
     if (!W.device_hash) return TE_OK;
     // verify_wait's launches without its wait, in the slot's own workspace
-    const size_t exp_b = W.nobj * n * TE_HASH_SIZE, dig_b = vi.size() * TE_HASH_SIZE, mask_b = W.nobj * sizeof(uint32_t);
-    TE_HIP(sl.ver.ensure(exp_b + dig_b + mask_b));
-    TE_HIP(sl.verh.ensure(exp_b + mask_b));
-    uint8_t *const d = sl.ver.as<uint8_t>();
-    uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + exp_b + dig_b);
-    memcpy(sl.verh.p, W.h_leaves, exp_b);
-    TE_HIP(hipMemcpyAsync(d, sl.verh.p, exp_b, hipMemcpyHostToDevice, s));
-    TE_HIP(hipMemsetAsync(d_mask, 0, mask_b, s));
-    if (int r = verify_enqueue(c, d_in, vi.data(), vi.size(), d, d + exp_b, nullptr, d_mask, s)) return r;
-    TE_HIP(hipMemcpyAsync(sl.verh.u8() + exp_b, d_mask, mask_b, hipMemcpyDeviceToHost, s));
-    if (!sl.verified) TE_HIP(hipEventCreateWithFlags(&sl.verified, hipEventDisableTiming | hipEventBlockingSync));
-    TE_HIP(hipEventRecord(sl.verified, s));
+    W.vl = VerLayout{W.nobj * n * TE_HASH_SIZE, vi.size() * TE_HASH_SIZE, results ? W.nobj * TE_HASH_SIZE : 0,
+                     W.nobj * sizeof(uint32_t), results ? 2u : 1u};
+    if (int r = ver_begin(sl.ver, sl.verh, W.vl, W.h_leaves, s)) return r;
+    if (int r = ver_masks(c, sl.ver, sl.verh, sl.in.as<uint8_t>(), vi, W.vl, 0, s)) return r;
+    if (!sl.peers) TE_HIP(hipEventCreateWithFlags(&sl.peers, hipEventDisableTiming | hipEventBlockingSync));
+    TE_HIP(hipEventRecord(sl.peers, s));
     st.slices_hashed_device += vi.size();
     return TE_OK;
 }
 
+// Stage A of a read window on slot k: the slices go up from the caller's buffer as they lie.
+int read_stage_a(te_clay *c, WinPipe &P, int k, ReadWin &W) {
+    WinPipe::Slot &sl = P.slot[k];
+    const hipStream_t s = read_slot_stream(c, k);
+    return peer_stage_a(
+        c, sl, s, W, W.objs, W.h_slices, true, false, c->rds, &te_read_launch_stats::slices_uploaded,
+        [&] { read_resolve(c, W); },
+        [&](const std::vector<CopyRun> &hin) { return copy_runs(hin, sl.in.as<uint8_t>(), W.h_slices, hipMemcpyHostToDevice, s); });
+}
+
 // The one host wait of a device-hashed window (its device current; the handle need not be locked).
-int read_wait_masks(ReadPipe &P, int k, const ReadWin &W) {
+int read_wait_masks(WinPipe &P, int k, const ReadWin &W) {
     if (!W.device_hash || W.resolved) return TE_OK;
-    TE_HIP(hipEventSynchronize(P.slot[k].verified));
+    TE_HIP(hipEventSynchronize(P.slot[k].peers));
     return TE_OK;
 }
 
 // Stage B (handle locked, its device current, read_wait_masks passed).
-int read_stage_b(te_clay *c, ReadPipe &P, int k, ReadWin &W) {
-    ReadPipe::Slot &sl = P.slot[k];
+int read_stage_b(te_clay *c, WinPipe &P, int k, ReadWin &W) {
+    WinPipe::Slot &sl = P.slot[k];
     const hipStream_t s = read_slot_stream(c, k);
     te_read_launch_stats &st = c->rds;
     if (!W.resolved) {
-        const size_t exp_b = W.nobj * (size_t)c->h.n * TE_HASH_SIZE;
-        memcpy(W.good.data(), sl.verh.u8() + exp_b, W.nobj * sizeof(uint32_t));
+        memcpy(W.good.data(), sl.verh.u8() + W.vl.h_mask(0), W.vl.mask_b);
         st.host_waits++;
         read_resolve(c, W);
     }
@@ -5122,7 +5144,7 @@ int read_stage_b(te_clay *c, ReadPipe &P, int k, ReadWin &W) {
 
 int read_drain(te_clay *c) {  // its device current
     int rc = TE_OK;
-    for (int k = 0; k < ReadPipe::R; k++)
+    for (int k = 0; k < WinPipe::R; k++)
         if (hipStream_t s = read_slot_stream(c, k)) {
             const int r = sync_sleep(s);
             if (!rc) rc = r;
@@ -5147,8 +5169,8 @@ int decode_host_impl(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slic
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     if (int r = read_streams(c)) return r;
-    if (!c->rpipe) c->rpipe = new ReadPipe();
-    ReadPipe &P = *c->rpipe;
+    if (!c->rpipe) c->rpipe = new WinPipe();
+    WinPipe &P = *c->rpipe;
     const size_t nw = cuts.size() - 1;
     const size_t n = (size_t)c->h.n;
     const char *co = tec_knob("TEC_READ_COPY_ONLY");  // read per call: a benchmark switches it between legs
@@ -5173,9 +5195,9 @@ int decode_host_impl(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slic
     // A(w + 1) before B(w): window w's host wait is spent with the next upload already queued
     int rc = TE_OK;
     for (size_t w = 0; w <= nw && !rc; w++) {
-        if (w < nw) rc = read_stage_a(c, P, (int)(w % ReadPipe::R), wins[w]);
+        if (w < nw) rc = read_stage_a(c, P, (int)(w % WinPipe::R), wins[w]);
         if (w > 0 && !rc) {
-            const int k = (int)((w - 1) % ReadPipe::R);
+            const int k = (int)((w - 1) % WinPipe::R);
             if (!(rc = read_wait_masks(P, k, wins[w - 1]))) rc = read_stage_b(c, P, k, wins[w - 1]);
         }
     }
@@ -5201,7 +5223,7 @@ struct te_stream_reader {
     struct Dev {
         te_clay *c = nullptr;
         int device = 0;
-        ReadPipe *P = nullptr;
+        WinPipe *P = nullptr;
         std::thread th;
         std::deque<std::shared_ptr<Job>> q;
         uint64_t nwin = 0;
@@ -5283,11 +5305,7 @@ int te_decode_window_plan(const te_clay *c, const te_decode_object *objs, const 
     *nwindows = 0;
     std::vector<size_t> v;
     if (int r = read_cuts(c, objs, h_meta, nobj, window_bytes, v)) return r;
-    *nwindows = v.size() - 1;
-    if (!cuts) return TE_OK;
-    if (cap < v.size()) return TE_ERR_BUFFER_TOO_SMALL;
-    memcpy(cuts, v.data(), v.size() * sizeof(size_t));
-    return TE_OK;
+    return cuts_out(v, cuts, cap, nwindows);
 }
 
 int te_decode_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_decode_object *objs,
@@ -5326,7 +5344,7 @@ int te_stream_reader_new(te_clay *const *coders, size_t ncoders, const te_slicer
         auto d = std::make_unique<te_stream_reader::Dev>();
         d->c = coders[i];
         d->device = coders[i]->device;
-        d->P = new ReadPipe();
+        d->P = new WinPipe();
         {
             std::lock_guard<std::mutex> lk(d->c->mu);
             DeviceGuard dg(d->device);
@@ -5379,7 +5397,7 @@ int te_stream_read_submit(te_stream_reader *r, const uint8_t *h_slices, const te
     const uint64_t t = r->next++;
     te_stream_reader::Dev &d = *r->devs[(size_t)((t - 1) % r->devs.size())];
     j->ticket = t;
-    j->slot = (int)(d.nwin++ % ReadPipe::R);
+    j->slot = (int)(d.nwin++ % WinPipe::R);
     r->tickets[t] = j;
     d.q.push_back(j);
     r->cv_work.notify_all();
@@ -5429,7 +5447,7 @@ void te_stream_reader_free(te_stream_reader *r) {
         std::lock_guard<std::mutex> lk(d->c->mu);
         DeviceGuard dg(d->device);
         (void)read_drain(d->c);
-        read_pipe_free(d->P);
+        win_pipe_free(d->P);
         d->P = nullptr;
     }
     delete r;
@@ -5440,8 +5458,9 @@ void te_stream_reader_free(te_stream_reader *r) {
 // ------------------------------------------------------------------------------------------
 // Host rebuild pipeline (te_repair_batch_host, te_recover_batch_host): the node's repair loop
 // (network/node/src/features/spool/repair.rs:94-226) and its escalation (recover.rs:77-244) behind
-// a host boundary, on the read pipeline's plan: windows (rebuild_cuts), window w on slot w mod 3 of
-// the handle's three streams, in three stages:
+// a host boundary, on the read pipeline's plan and its pieces (listed above it): windows
+// (window_cuts), window w on slot w mod 3 of the handle's three streams (a WinPipe of its own), a
+// recover window's stage A the read's peer_stage_a with rebuild_upload for the copies; three stages:
 //   A  pick who hashes; recover with host hashing: the pool hashes the peer slices where they lie
 //      and the survivor sets are final; enqueue the H2D copies (repair: the plan's fragments,
 //      packed; recover: each slice to its slot of the object's n * slice_len range); recover with
@@ -5455,28 +5474,6 @@ void te_stream_reader_free(te_stream_reader *r) {
 // ------------------------------------------------------------------------------------------
 namespace {
 
-struct RebuildPipe {
-    static constexpr int R = te_clay::kPipe;
-    struct Slot {
-        DevBuf in, out;     // the window's fragments / slices and rebuilt slices
-        DevBuf ver;         // device hashing: expected leaves | digests | peer masks | result masks
-        HostBuf verh;       // its page-locked host side: expected leaves | peer masks | result masks
-        HostBuf hin, hout;  // page-locked staging of pageable caller buffers
-        hipEvent_t peers = nullptr, done = nullptr;
-    } slot[R];
-};
-
-void rebuild_pipe_free(RebuildPipe *p) {  // its streams drained, its device current
-    if (!p) return;
-    for (auto &sl : p->slot) {
-        for (DevBuf *b : {&sl.in, &sl.out, &sl.ver}) b->release();
-        for (HostBuf *b : {&sl.verh, &sl.hin, &sl.hout}) b->release();
-        if (sl.peers) (void)hipEventDestroy(sl.peers);
-        if (sl.done) (void)hipEventDestroy(sl.done);
-    }
-    delete p;
-}
-
 // The bytes of helper `sl`'s fragment under plan p (te_extract_repair_data_size for every slice).
 void plan_needs(const te_repair_plan *p, uint64_t *need) {
     std::fill(need, need + p->n, 0ull);
@@ -5485,20 +5482,6 @@ void plan_needs(const te_repair_plan *p, uint64_t *need) {
 }
 
 inline uint64_t plan_out_bytes(const te_repair_plan *p) { return (uint64_t)p->ns * p->cs + TE_META_SIZE; }
-
-void rebuild_cuts(const std::vector<uint64_t> &bytes, size_t window_bytes, std::vector<size_t> &cuts) {
-    if (window_bytes == 0) window_bytes = (size_t)128 << 20;
-    cuts.assign(1, 0);
-    uint64_t sum = 0;
-    for (size_t i = 0; i < bytes.size(); i++) {
-        if (i > cuts.back() && sum + bytes[i] > window_bytes) {
-            cuts.push_back(i);
-            sum = 0;
-        }
-        sum += bytes[i];
-    }
-    if (!bytes.empty()) cuts.push_back(bytes.size());
-}
 
 int repair_object_bytes(const te_clay *c, const te_repair_object *objs, size_t nobj, std::vector<uint64_t> &bytes) {
     bytes.resize(nobj);
@@ -5518,14 +5501,6 @@ void recover_object_bytes(const te_clay *c, const te_recover_object *objs, size_
     bytes.resize(nobj);
     for (size_t i = 0; i < nobj; i++)
         bytes[i] = ((uint64_t)__builtin_popcount(objs[i].avail_mask & all) + 1u) * objs[i].slice_len;
-}
-
-int cuts_out(const std::vector<size_t> &v, size_t *cuts, size_t cap, size_t *nwindows) {
-    *nwindows = v.size() - 1;
-    if (!cuts) return TE_OK;
-    if (cap < v.size()) return TE_ERR_BUFFER_TOO_SMALL;
-    memcpy(cuts, v.data(), v.size() * sizeof(size_t));
-    return TE_OK;
 }
 
 // One window: nobj objects of the caller's arrays (already offset to the window's first object).
@@ -5553,52 +5528,17 @@ struct RebuildWin {
     std::vector<uint64_t> out_dev, out_len, out_host;  // per object: its rebuilt slice on the device / host
     std::vector<uint32_t> lost;
     std::vector<CopyRun> hout;
-    uint64_t out_sz = 0, npeers = 0;
+    uint64_t out_sz = 0;
+    VerLayout vl{};  // device hashing: the slot's verify workspace
 };
-
-struct HashItem { const uint8_t *p; uint64_t len; const uint8_t *expect; };
-
-// hash_leaf of the items on the host pool against their expected hashes; waits for the pool.
-void hash_items_host(const std::vector<HashItem> &items, int device, std::vector<uint8_t> &okv) {
-    okv.assign(items.size(), 0);
-    if (items.empty()) return;
-    hh::Pool &pool = hh::Pool::get();
-    const int lanes = (int)std::max<size_t>(1, std::min<size_t>((size_t)pool.lanes(), items.size() / (size_t)std::max(1, pool.threads())));
-    auto ok = std::make_shared<std::vector<uint8_t>>(items.size(), 0);
-    auto job = std::make_shared<hh::Job>();
-    std::vector<std::function<void()>> tasks;
-    for (size_t j0 = 0; j0 < items.size();) {
-        size_t j1 = j0 + 1;  // a task's lanes hash messages of one length
-        while (j1 < items.size() && j1 - j0 < (size_t)lanes && items[j1].len == items[j0].len) j1++;
-        std::vector<HashItem> part(items.begin() + (ptrdiff_t)j0, items.begin() + (ptrdiff_t)j1);
-        tasks.push_back([part, j0, ok, job] {
-            const int L = (int)part.size();
-            uint8_t dig[hh::kMaxLanes][TE_HASH_SIZE];
-            const uint8_t *src[hh::kMaxLanes];
-            uint8_t *dst[hh::kMaxLanes];
-            for (int l = 0; l < L; l++) {
-                src[l] = part[(size_t)l].p;
-                dst[l] = dig[l];
-            }
-            hh::hash_leaves(L, src, part[0].len, dst);
-            for (int l = 0; l < L; l++) (*ok)[j0 + (size_t)l] = memcmp(dig[l], part[(size_t)l].expect, TE_HASH_SIZE) == 0;
-            job->done();
-        });
-        j0 = j1;
-    }
-    job->add((int64_t)tasks.size());
-    pool.submit_after(nullptr, device, std::move(tasks));
-    (void)job->wait();
-    okv = *ok;
-}
 
 // The window's H2D copies: pinned memory directly, pageable memory gathered by the copy pool into
 // the slot's page-locked staging first (one DMA per run instead of one driver-staged copy).
-int rebuild_upload(te_clay *c, RebuildPipe::Slot &sl, const RebuildWin &W, const std::vector<CopyRun> &runs, hipStream_t s) {
+int rebuild_upload(te_clay *c, WinPipe::Slot &sl, const RebuildWin &W, const std::vector<CopyRun> &runs, hipStream_t s) {
     uint8_t *const d_in = sl.in.as<uint8_t>();
     if (W.pinned_in) return copy_runs(runs, d_in, W.h_in, hipMemcpyHostToDevice, s);
     uint64_t total = 0;
-    for (const CopyRun &r : runs) total += (r.len + 15) & ~15ull;
+    for (const CopyRun &r : runs) total += align16(r.len);
     if (!total) return TE_OK;
     TE_HIP(sl.hin.ensure(total));
     std::vector<tec::CopyPool::Seg> segs;
@@ -5606,11 +5546,8 @@ int rebuild_upload(te_clay *c, RebuildPipe::Slot &sl, const RebuildWin &W, const
     uint64_t at = 0;
     for (const CopyRun &r : runs) {
         segs.push_back({sl.hin.u8() + at, W.h_in + r.host, (size_t)r.len});
-        if (!staged.empty() && staged.back().host + staged.back().len == at && staged.back().dev + staged.back().len == r.dev)
-            staged.back().len += r.len;
-        else
-            staged.push_back({at, r.dev, r.len});
-        at += (r.len + 15) & ~15ull;
+        add_run(staged, at, r.dev, r.len);
+        at += align16(r.len);
     }
     copy_pool(c->device).run(segs);
     return copy_runs(staged, d_in, sl.hin.u8(), hipMemcpyHostToDevice, s);
@@ -5624,143 +5561,48 @@ void recover_resolve(const te_clay *c, RebuildWin &W) {
     W.hout.clear();
     W.out_sz = 0;
     for (size_t o = 0; o < W.nobj; o++) {
-        const uint32_t avail = W.rec[o].avail_mask & all, ok = avail & W.good[o];
-        if (W.h_leaves && W.h_rej) W.h_rej[o] = avail & ~ok;
-        int st = W.pre ? W.pre[o] : TE_OK;
         DecItem it{};
-        if (!st) st = decode_validate(c, W.h_meta + o * TE_META_SIZE, W.rec[o].slice_len, ok, it);
-        if (W.h_status) W.h_status[o] = st;
+        // h_rej is written only when leaves were given
+        const int st = resolve_survivors(c, W.rec[o].avail_mask & all, W.rec[o].slice_len, W.h_meta + o * TE_META_SIZE,
+                                         W.pre ? W.pre[o] : TE_OK, W.good[o], W.h_leaves && W.h_rej ? W.h_rej + o : nullptr,
+                                         W.h_status ? W.h_status + o : nullptr, W.good[o], it);
         if (W.h_leaves && W.h_ok) W.h_ok[o] = 0;  // unverified: h_ok is not the call's to write
-        W.good[o] = st ? 0u : ok;
         if (st) continue;
         W.run.push_back(o);
         W.out_dev[o] = W.out_sz;
-        if (!W.hout.empty() && W.hout.back().host + W.hout.back().len == W.out_host[o] &&
-            W.hout.back().dev + W.hout.back().len == W.out_sz)
-            W.hout.back().len += W.out_len[o];
-        else
-            W.hout.push_back({W.out_host[o], W.out_sz, W.out_len[o]});
-        W.out_sz += (W.out_len[o] + 15) & ~15ull;  // device copies 16-byte aligned
+        add_run(W.hout, W.out_host[o], W.out_sz, W.out_len[o]);
+        W.out_sz += align16(W.out_len[o]);
     }
     W.resolved = true;
 }
 
-// The slot's verify workspace: expected leaves | digests (peers, results) | peer masks | result masks.
-struct VerLayout {
-    size_t exp_b, dig_p, dig_o, mask_b;
-    size_t dig_off() const { return exp_b; }
-    size_t mask_p_off() const { return exp_b + dig_p + dig_o; }
-    size_t mask_o_off() const { return mask_p_off() + mask_b; }
-    size_t total() const { return mask_o_off() + mask_b; }
-    size_t h_mask_p() const { return exp_b; }
-    size_t h_mask_o() const { return exp_b + mask_b; }
-    size_t h_total() const { return exp_b + 2 * mask_b; }
-};
-VerLayout ver_layout(const te_clay *c, const RebuildWin &W) {
-    return VerLayout{W.nobj * (size_t)c->h.n * TE_HASH_SIZE, (size_t)W.npeers * TE_HASH_SIZE, W.nobj * TE_HASH_SIZE,
-                     W.nobj * sizeof(uint32_t)};
-}
-
-// Device hashing: the window's expected leaves and zeroed masks on the device (stage A).
-int rebuild_ver_begin(te_clay *c, RebuildPipe::Slot &sl, const RebuildWin &W, hipStream_t s) {
-    const VerLayout L = ver_layout(c, W);
-    TE_HIP(sl.ver.ensure(L.total()));
-    TE_HIP(sl.verh.ensure(L.h_total()));
-    memcpy(sl.verh.p, W.h_leaves, L.exp_b);
-    TE_HIP(hipMemcpyAsync(sl.ver.p, sl.verh.p, L.exp_b, hipMemcpyHostToDevice, s));
-    TE_HIP(hipMemsetAsync(sl.ver.as<uint8_t>() + L.mask_p_off(), 0, 2 * L.mask_b, s));
-    return TE_OK;
-}
-
-// Stage A of a recover window on slot k (handle locked, its device current).
-int recover_stage_a(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
-    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
-    RebuildPipe::Slot &sl = P.slot[k];
+// Stage A of a recover window on slot k: peer_stage_a with a rebuilt slice per object to verify
+// afterwards, and rebuild_upload for the slices.
+int recover_stage_a(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
+    WinPipe::Slot &sl = P.slot[k];
     const hipStream_t s = read_slot_stream(c, k);
-    te_rebuild_launch_stats &st = c->rbs;
-    st.windows++;
-    st.objects += W.nobj;
-    W.in_base.resize(W.nobj);
-    W.good.assign(W.nobj, 0);
     W.out_dev.assign(W.nobj, 0);
     W.out_len.resize(W.nobj);
     W.out_host.resize(W.nobj);
     W.lost.resize(W.nobj);
-    uint64_t in_sz = 0, max_slice = 0, slice_bytes = 0, nslices = 0;
-    bool dword = true;
+    bool dword = true;  // the recover kernels' and the rebuilt slice's verify item's alignment
     for (size_t o = 0; o < W.nobj; o++) {
         const te_recover_object &ob = W.rec[o];
-        W.in_base[o] = in_sz;
-        in_sz += ((uint64_t)n * ob.slice_len + 15) & ~15ull;
         W.out_len[o] = ob.slice_len;
         W.out_host[o] = ob.out_off;
         W.lost[o] = ob.lost;
-        const uint64_t np = (uint64_t)__builtin_popcount(ob.avail_mask & all);
-        nslices += np;
-        slice_bytes += np * ob.slice_len;
-        if (np) max_slice = std::max<uint64_t>(max_slice, ob.slice_len);
-        dword = dword && ob.slice_len % 4u == 0 && ob.slices_off % 4u == 0 && ob.out_off % 4u == 0;
+        dword = dword && ob.slices_off % 4u == 0 && ob.out_off % 4u == 0;
     }
-    W.device_hash = W.h_leaves && !W.copy_only && nslices && dword && !host_hash_wins(W.mode, nslices, max_slice, slice_bytes);
-    if (!W.h_leaves || W.copy_only) {
-        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.rec[o].avail_mask & all;
-        recover_resolve(c, W);
-    } else if (!W.device_hash) {
-        std::vector<HashItem> items;
-        std::vector<std::pair<uint32_t, uint32_t>> who;
-        for (size_t o = 0; o < W.nobj; o++)
-            for (uint32_t b = 0; b < n; b++)
-                if (((W.rec[o].avail_mask & all) >> b) & 1u) {
-                    items.push_back({W.h_in + W.rec[o].slices_off + (uint64_t)b * W.rec[o].slice_len, W.rec[o].slice_len,
-                                     W.h_leaves + (o * n + b) * TE_HASH_SIZE});
-                    who.push_back({(uint32_t)o, b});
-                }
-        std::vector<uint8_t> ok;
-        hash_items_host(items, c->device, ok);
-        for (size_t j = 0; j < items.size(); j++)
-            if (ok[j]) W.good[who[j].first] |= 1u << who[j].second;
-        st.slices_hashed_host += items.size();
-        recover_resolve(c, W);
-    } else {
-        for (size_t o = 0; o < W.nobj; o++) W.good[o] = W.rec[o].avail_mask & all;  // every present slice goes up
-    }
-    TE_HIP(sl.in.ensure(in_sz + 16));
-    std::vector<CopyRun> hin;
-    std::vector<te_verify_item> vi;
-    for (size_t o = 0; o < W.nobj; o++) {
-        const uint64_t len = W.rec[o].slice_len;
-        for (uint32_t b = 0; b < n; b++) {
-            if (!((W.good[o] >> b) & 1u) || !len) continue;
-            const uint64_t host = W.rec[o].slices_off + (uint64_t)b * len, dev = W.in_base[o] + (uint64_t)b * len;
-            if (!hin.empty() && hin.back().host + hin.back().len == host && hin.back().dev + hin.back().len == dev)
-                hin.back().len += len;
-            else
-                hin.push_back({host, dev, len});
-            st.pieces_uploaded++;
-            st.bytes_h2d += len;
-        }
-        if (W.device_hash) verify_push_slices(vi, o, n, W.in_base[o], len, W.good[o]);
-    }
-    if (int r = rebuild_upload(c, sl, W, hin, s)) return r;
-    if (!W.device_hash) return TE_OK;
-    W.npeers = vi.size();
-    if (int r = rebuild_ver_begin(c, sl, W, s)) return r;
-    const VerLayout L = ver_layout(c, W);
-    uint8_t *const d = sl.ver.as<uint8_t>();
-    uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + L.mask_p_off());
-    if (int r = verify_enqueue(c, sl.in.as<uint8_t>(), vi.data(), vi.size(), d, d + L.dig_off(), nullptr, d_mask, s)) return r;
-    TE_HIP(hipMemcpyAsync(sl.verh.u8() + L.h_mask_p(), d_mask, L.mask_b, hipMemcpyDeviceToHost, s));
-    if (!sl.peers) TE_HIP(hipEventCreateWithFlags(&sl.peers, hipEventDisableTiming | hipEventBlockingSync));
-    TE_HIP(hipEventRecord(sl.peers, s));
-    st.slices_hashed_device += vi.size();
-    return TE_OK;
+    return peer_stage_a(c, sl, s, W, W.rec, W.h_in, dword, true, c->rbs, &te_rebuild_launch_stats::pieces_uploaded,
+                        [&] { recover_resolve(c, W); },
+                        [&](const std::vector<CopyRun> &hin) { return rebuild_upload(c, sl, W, hin, s); });
 }
 
 // Stage A of a repair window: the plan's fragments, packed (each 16-byte aligned, as
 // te_slicer_repair places them); the repair kernels address them through helper_off.
-int repair_stage_a(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
+int repair_stage_a(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
     const uint32_t n = (uint32_t)c->h.n;
-    RebuildPipe::Slot &sl = P.slot[k];
+    WinPipe::Slot &sl = P.slot[k];
     const hipStream_t s = read_slot_stream(c, k);
     te_rebuild_launch_stats &st = c->rbs;
     st.windows++;
@@ -5782,12 +5624,8 @@ int repair_stage_a(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
         for (uint32_t b = 0; b < n; b++) {
             if (!need[b]) continue;
             W.frag_off[o * n + b] = in_sz;
-            const uint64_t host = W.rep[o].helper_off[b];
-            if (!hin.empty() && hin.back().host + hin.back().len == host && hin.back().dev + hin.back().len == in_sz)
-                hin.back().len += need[b];
-            else
-                hin.push_back({host, in_sz, need[b]});
-            in_sz += (need[b] + 15) & ~15ull;
+            add_run(hin, W.rep[o].helper_off[b], in_sz, need[b]);
+            in_sz += align16(need[b]);
             st.pieces_uploaded++;
             st.bytes_h2d += need[b];
         }
@@ -5796,12 +5634,8 @@ int repair_stage_a(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
         W.out_len[o] = plan_out_bytes(p);
         W.out_host[o] = W.rep[o].out_off;
         W.out_dev[o] = W.out_sz;
-        if (!W.hout.empty() && W.hout.back().host + W.hout.back().len == W.out_host[o] &&
-            W.hout.back().dev + W.hout.back().len == W.out_sz)
-            W.hout.back().len += W.out_len[o];
-        else
-            W.hout.push_back({W.out_host[o], W.out_sz, W.out_len[o]});
-        W.out_sz += (W.out_len[o] + 15) & ~15ull;
+        add_run(W.hout, W.out_host[o], W.out_sz, W.out_len[o]);
+        W.out_sz += align16(W.out_len[o]);
         max_len = std::max(max_len, W.out_len[o]);
         sum_len += W.out_len[o];
         dword = dword && W.out_len[o] % 4u == 0 && W.out_host[o] % 4u == 0;
@@ -5810,21 +5644,21 @@ int repair_stage_a(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
     W.resolved = true;
     TE_HIP(sl.in.ensure(in_sz + 16));
     if (int r = rebuild_upload(c, sl, W, hin, s)) return r;
-    if (W.device_hash) return rebuild_ver_begin(c, sl, W, s);
-    return TE_OK;
+    if (!W.device_hash) return TE_OK;
+    W.vl = VerLayout{W.nobj * n * TE_HASH_SIZE, 0, W.nobj * TE_HASH_SIZE, W.nobj * sizeof(uint32_t), 2};  // no peers
+    return ver_begin(sl.ver, sl.verh, W.vl, W.h_leaves, s);
 }
 
 // Stage B (handle locked, its device current): the kernels, the rebuilt slices' hashes, the D2H copies.
-int rebuild_stage_b(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
+int rebuild_stage_b(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
     const uint32_t n = (uint32_t)c->h.n;
-    RebuildPipe::Slot &sl = P.slot[k];
+    WinPipe::Slot &sl = P.slot[k];
     const hipStream_t s = read_slot_stream(c, k);
     te_rebuild_launch_stats &st = c->rbs;
-    const VerLayout L = ver_layout(c, W);
     if (!W.resolved) {  // recover, device hashing: the window's wait for its peers' masks
         TE_HIP(hipEventSynchronize(sl.peers));
         st.host_waits++;
-        memcpy(W.good.data(), sl.verh.u8() + L.h_mask_p(), W.nobj * sizeof(uint32_t));
+        memcpy(W.good.data(), sl.verh.u8() + W.vl.h_mask(0), W.vl.mask_b);
         recover_resolve(c, W);
     }
     if (!sl.done) TE_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming | hipEventBlockingSync));
@@ -5850,10 +5684,7 @@ int rebuild_stage_b(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
             std::vector<te_verify_item> vi;
             for (size_t o : W.run)
                 vi.push_back(te_verify_item{W.out_dev[o], W.out_len[o], (uint32_t)(o * n + W.lost[o]), (uint32_t)o, 1u, 0});
-            uint8_t *const d = sl.ver.as<uint8_t>();
-            uint32_t *const d_mask = reinterpret_cast<uint32_t *>(d + L.mask_o_off());
-            if (int r = verify_enqueue(c, d_out, vi.data(), vi.size(), d, d + L.dig_off() + L.dig_p, nullptr, d_mask, s)) return r;
-            TE_HIP(hipMemcpyAsync(sl.verh.u8() + L.h_mask_o(), d_mask, L.mask_b, hipMemcpyDeviceToHost, s));
+            if (int r = ver_masks(c, sl.ver, sl.verh, d_out, vi, W.vl, 1, s)) return r;
             st.slices_hashed_device += vi.size();
         }
         for (const CopyRun &r : W.hout) st.bytes_d2h += r.len;
@@ -5869,8 +5700,8 @@ int rebuild_stage_b(te_clay *c, RebuildPipe &P, int k, RebuildWin &W) {
 }
 
 // Stage C (its device current): the window's results are on the host.
-int rebuild_stage_c(te_clay *c, RebuildPipe &P, int k, RebuildWin &W, bool last) {
-    RebuildPipe::Slot &sl = P.slot[k];
+int rebuild_stage_c(te_clay *c, WinPipe &P, int k, RebuildWin &W, bool last) {
+    WinPipe::Slot &sl = P.slot[k];
     te_rebuild_launch_stats &st = c->rbs;
     TE_HIP(hipEventSynchronize(sl.done));
     if (W.run.empty()) return TE_OK;
@@ -5883,8 +5714,7 @@ int rebuild_stage_c(te_clay *c, RebuildPipe &P, int k, RebuildWin &W, bool last)
     }
     if (!verified) return TE_OK;
     if (W.device_hash) {
-        const VerLayout L = ver_layout(c, W);
-        const uint32_t *m = reinterpret_cast<const uint32_t *>(sl.verh.u8() + L.h_mask_o());
+        const uint32_t *m = reinterpret_cast<const uint32_t *>(sl.verh.u8() + W.vl.h_mask(1));
         for (size_t o : W.run) W.h_ok[o] = m[o] & 1u;
         return TE_OK;
     }
@@ -5902,15 +5732,15 @@ int rebuild_stage_c(te_clay *c, RebuildPipe &P, int k, RebuildWin &W, bool last)
 // The driver: handle locked, its device current, the windows filled in.
 int rebuild_run(te_clay *c, std::vector<RebuildWin> &wins) {
     if (int r = read_streams(c)) return r;
-    if (!c->rbpipe) c->rbpipe = new RebuildPipe();
-    RebuildPipe &P = *c->rbpipe;
+    if (!c->rbpipe) c->rbpipe = new WinPipe();
+    WinPipe &P = *c->rbpipe;
     const size_t nw = wins.size();
     int rc = TE_OK;
     for (size_t w = 0; w < nw + 2 && !rc; w++) {
-        if (w < nw) rc = wins[w].rep ? repair_stage_a(c, P, (int)(w % RebuildPipe::R), wins[w])
-                                     : recover_stage_a(c, P, (int)(w % RebuildPipe::R), wins[w]);
-        if (!rc && w >= 1 && w - 1 < nw) rc = rebuild_stage_b(c, P, (int)((w - 1) % RebuildPipe::R), wins[w - 1]);
-        if (!rc && w >= 2) rc = rebuild_stage_c(c, P, (int)((w - 2) % RebuildPipe::R), wins[w - 2], w - 2 == nw - 1);
+        if (w < nw) rc = wins[w].rep ? repair_stage_a(c, P, (int)(w % WinPipe::R), wins[w])
+                                     : recover_stage_a(c, P, (int)(w % WinPipe::R), wins[w]);
+        if (!rc && w >= 1 && w - 1 < nw) rc = rebuild_stage_b(c, P, (int)((w - 1) % WinPipe::R), wins[w - 1]);
+        if (!rc && w >= 2) rc = rebuild_stage_c(c, P, (int)((w - 2) % WinPipe::R), wins[w - 2], w - 2 == nw - 1);
     }
     // also after a failure: copies from and to the caller's buffers may still be queued
     const int r2 = read_drain(c);
@@ -5936,7 +5766,7 @@ int te_repair_window_plan(const te_clay *c, const te_repair_object *objs, size_t
     std::vector<uint64_t> bytes;
     if (int r = repair_object_bytes(c, objs, nobj, bytes)) return r;
     std::vector<size_t> v;
-    rebuild_cuts(bytes, window_bytes, v);
+    window_cuts(bytes, window_bytes, v);
     return cuts_out(v, cuts, cap, nwindows);
 }
 
@@ -5947,7 +5777,7 @@ int te_recover_window_plan(const te_clay *c, const te_recover_object *objs, size
     std::vector<uint64_t> bytes;
     recover_object_bytes(c, objs, nobj, bytes);
     std::vector<size_t> v;
-    rebuild_cuts(bytes, window_bytes, v);
+    window_cuts(bytes, window_bytes, v);
     return cuts_out(v, cuts, cap, nwindows);
 }
 
@@ -5967,7 +5797,7 @@ int te_repair_batch_host(te_clay *c, const uint8_t *h_helpers, const te_repair_o
     std::vector<uint64_t> bytes;
     if (int r = repair_object_bytes(c, objs, nobj, bytes)) return r;
     std::vector<size_t> cuts;
-    rebuild_cuts(bytes, window_bytes, cuts);
+    window_cuts(bytes, window_bytes, cuts);
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
     std::lock_guard<std::mutex> lk(c->mu);
     c->rls = te_repair_launch_stats{};
@@ -6017,7 +5847,7 @@ int te_recover_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h
     std::vector<uint64_t> bytes;
     recover_object_bytes(c, objs, nobj, bytes);
     std::vector<size_t> cuts;
-    rebuild_cuts(bytes, window_bytes, cuts);
+    window_cuts(bytes, window_bytes, cuts);
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
     std::lock_guard<std::mutex> lk(c->mu);
     c->dls = te_decode_launch_stats{};
