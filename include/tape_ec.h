@@ -577,6 +577,78 @@ int te_commit_batch_device(const uint8_t *d_slices, uint64_t obj_stride, uint64_
                            uint8_t *d_proofs, void *hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Data verify: the verify half of the read flow.  verify_track_data (sdk/src/track/read.rs:145-186)
+ * re-encodes an object's bytes with BlobEncoder::encode_with_root (sdk/src/codec/encoder.rs:166-193:
+ * Slicer::encode, hash_leaf per slice, root_from_leaf_hashes) and compares the root with the
+ * on-chain blob.commitment (read.rs:174-185).  Here the slices never leave HBM: the object's bytes
+ * go up, 32 + 4 (+ 8) bytes per object come back.
+ * ------------------------------------------------------------------------------------------ */
+/* Root and check of nobj objects from their leaf hashes (DEVICE pointers, enqueued on hip_stream,
+ * not waited for; read.rs:174-185 after encoder.rs:166-193's hashing).  Object o's n leaf hashes
+ * at d_leaf_hashes + o*n*32 (as te_commit_batch_device writes them), its expected root at
+ * d_expected_roots + o*32 and, if d_expected_leaves is not NULL, its BlobEncoding::leaves at
+ * d_expected_leaves + o*n*32.  Outputs: d_roots + o*32 (or NULL) the observed root
+ * root_from_leaf_hashes::<height>; d_ok[o] = 1 if it equals the expected root, else 0;
+ * d_bad_leaf_mask[o] (or NULL; written only when d_expected_leaves is given) bit i set iff leaf i
+ * differs from expected leaf i.  One wave per object.  TE_ERR_INVALID_ARG: n == 0, n > 64,
+ * height > 32, n > 2^height, a NULL required pointer, a hash pointer that is not 4-byte aligned. */
+int te_roots_check_device(const uint8_t *d_leaf_hashes, uint32_t n, size_t nobj, uint32_t height,
+                          const uint8_t *d_expected_roots, const uint8_t *d_expected_leaves,
+                          uint8_t *d_roots, uint32_t *d_ok, uint64_t *d_bad_leaf_mask, void *hip_stream);
+/* verify_track_data's coded branch (read.rs:174-185; encoder.rs:166-193) over a batch, on the
+ * device (DEVICE pointers, `objs` a host array; enqueued on hip_stream, nothing waited for): object
+ * o's bytes at d_data + objs[o].data_off are encoded (te_encode_batch_device; chunk_index is part
+ * of the 48-byte suffix and so of every leaf), each slice hashed and the root checked
+ * (te_roots_check_device's outputs and optional arguments).  objs[o].out_off is ignored: the call
+ * lays the slices out itself in d_work (te_verify_data_work_bytes bytes, 16-byte aligned; slices
+ * 4-aligned, back to back, then the leaf hashes, which stay there for the caller: object o's at
+ * d_work + te_verify_data_work_bytes - (nobj - o)*n*32).  Objects of different slice lengths are
+ * hashed in runs of equal length, one leaf launch series per run.  A work_bytes below
+ * te_verify_data_work_bytes is TE_ERR_BUFFER_TOO_SMALL.  Requires n <= 64, 1 <= height <= 32,
+ * n <= 2^height and slice_len % 4 == 0. */
+size_t te_verify_data_work_bytes(const te_clay *c, const te_object *objs, size_t nobj);
+int te_verify_data_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data,
+                                const te_object *objs, size_t nobj, uint32_t height,
+                                const uint8_t *d_expected_roots, const uint8_t *d_expected_leaves,
+                                uint8_t *d_work, size_t work_bytes,
+                                uint8_t *d_roots, uint32_t *d_ok, uint64_t *d_bad_leaf_mask, void *hip_stream);
+/* The same HOST -> HOST (read.rs:174-185 / encoder.rs:166-193 over a batch): te_encode_commit_batch_host's
+ * pipeline -- the same groups of at most `window_bytes` (input + slices; 0 = 8 GiB here: a group
+ * costs one slice's hash chain whatever it holds, so fewer are faster) and copy windows, the H2D
+ * and encode of one window beside the leaf launches of the group before -- with the slice D2H
+ * switched off: per group the only copies back are the results, at most 32 + 4 + 8 bytes per
+ * object.  h_expected_leaves, h_roots and h_bad_leaf_mask may be NULL.  Hashing is always on the
+ * device: te_set_commit_hashing does not affect these calls (TE_HASH_HOST needs the slices on the
+ * host, the copy this path removes).  What bounds it: one slice's SHA-256 chain per group (~24 MB/s
+ * per lane, ~29 ms for a 4 MiB object's 715 KB slices), then the H2D copy: 1024 x 4 MiB objects
+ * verify in 137 ms against 337 ms on te_encode_commit_batch_host.  The crossover: for slices above
+ * about 3 MB (objects above about 18 MB; the SDK's 64 MiB chunks have 9.7 MB slices, ~0.4 s per
+ * group: 435 against 195 ms for 32 of them) te_encode_commit_batch_host with host hashing remains
+ * the faster route to the same roots.
+ * h_data should be pinned for full PCIe rate; pageable memory works.  Synchronous. */
+int te_verify_data_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_data,
+                              const te_object *objs, size_t nobj, uint32_t height,
+                              const uint8_t *h_expected_roots, const uint8_t *h_expected_leaves,
+                              uint8_t *h_roots, uint32_t *h_ok, uint64_t *h_bad_leaf_mask,
+                              size_t window_bytes);
+/* verify_track_data for one object (read.rs:174-185; encoder.rs:166-193): one window of one
+ * object through the handle's staging buffers (`data` may be pageable).  *ok = 1 if the root of
+ * Slicer::encode(data) under cfg equals expected_root, else 0; observed_root (or NULL) receives
+ * the root.  Synchronous. */
+int te_slicer_verify_data(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *data, size_t len,
+                          uint32_t height, const uint8_t expected_root[TE_HASH_SIZE],
+                          uint8_t observed_root[TE_HASH_SIZE], int *ok);
+/* The handle's last data-verify call (device batch, host batch or per-call): its objects, copy
+ * windows, hashing groups (runs of equal slice length for the device forms), leaf_kernel and
+ * root-check launches, and the bytes that crossed PCIe: h2d_bytes the objects' data,
+ * h2d_expected_bytes the expected roots and leaves, d2h_bytes the results (no slice byte). */
+typedef struct te_verify_data_stats {
+    uint64_t objects, windows, groups, leaf_launches, root_check_launches;
+    uint64_t h2d_bytes, h2d_expected_bytes, d2h_bytes;
+} te_verify_data_stats;
+int te_clay_verify_data_launch_stats(te_clay *c, te_verify_data_stats *out);
+
+/* ------------------------------------------------------------------------------------------
  * Verified reads: the read side of the commitments.  Every reader of the reference checks a
  * slice against the object's leaves (BlobEncoding::leaves) before or after it touches the codec:
  * the gateway's object read (network/gateway/src/http/handlers/object/decode.rs:121-139), node

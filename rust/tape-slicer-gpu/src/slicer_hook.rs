@@ -100,6 +100,40 @@ impl ClayCoder {
         })
     }
 
+    /// `Slicer::verify_data`: verify_track_data's coded branch (sdk/src/track/read.rs:174-185) in one
+    /// te_slicer_verify_data -- BlobEncoder::encode_with_root (sdk/src/codec/encoder.rs:166-193:
+    /// Slicer::encode, hash_leaf per slice, root_from_leaf_hashes::<SLICE_TREE_HEIGHT>) on the
+    /// device and the compare with the on-chain commitment.  The slices never leave the device:
+    /// the object's bytes go up, the verdict and the observed root come back.
+    pub fn verify_data(&mut self, cfg: &ObjectCfg, data: &[u8], commitment: &[u8; 32]) -> Result<bool, EncodeError> {
+        self.verify_data_root(cfg, data, commitment).map(|(ok, _)| ok)
+    }
+
+    /// The root alone (encode_with_root's second result, encoder.rs:166-193).
+    pub fn encode_root(&mut self, cfg: &ObjectCfg, data: &[u8]) -> Result<[u8; 32], EncodeError> {
+        self.verify_data_root(cfg, data, &[0u8; 32]).map(|(_, root)| root)
+    }
+
+    fn verify_data_root(&mut self, cfg: &ObjectCfg, data: &[u8], expected: &[u8; 32])
+                        -> Result<(bool, [u8; 32]), EncodeError> {
+        let (mut root, mut ok) = ([0u8; 32], 0i32);
+        let c = cfg.ffi();
+        let r = unsafe {
+            ffi::te_slicer_verify_data(self.raw.as_ptr(), &c, data.as_ptr(), data.len(), ffi::TE_SLICE_TREE_HEIGHT as u32,
+                                       expected.as_ptr(), root.as_mut_ptr(), &mut ok)
+        };
+        encode_status(r).map(|_| (ok == 1, root))
+    }
+
+    /// Objects, windows, groups, launches and PCIe bytes of the last data-verify call on this handle.
+    pub fn verify_data_launch_stats(&mut self) -> ffi::te_verify_data_stats {
+        let mut st = ffi::te_verify_data_stats { objects: 0, windows: 0, groups: 0, leaf_launches: 0, root_check_launches: 0,
+                                                 h2d_bytes: 0, h2d_expected_bytes: 0, d2h_bytes: 0 };
+        let s = unsafe { ffi::te_clay_verify_data_launch_stats(self.raw.as_ptr(), &mut st) };
+        assert_eq!(s, 0, "te_clay_verify_data_launch_stats");
+        st
+    }
+
     /// A ranged object read -- Slicer::decode (slicer.rs:298-364) then `bytes[start..start + len]`,
     /// what the gateway's object_response_ranged does per track (routes.rs:90-91, response.rs:167-169)
     /// -- in one te_slicer_decode_range, which touches only the window's stripes.  A multi-track

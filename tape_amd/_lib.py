@@ -164,6 +164,11 @@ class te_snapshot_stats(C.Structure):
                                           "commit_launches", "host_waits")]
 
 
+class te_verify_data_stats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("objects", "windows", "groups", "leaf_launches", "root_check_launches",
+                                          "h2d_bytes", "h2d_expected_bytes", "d2h_bytes")]
+
+
 def build(verbose: bool = False) -> str:
     """Compile libtapeec.so for gfx950 with hipcc (make -C tape_amd)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True,
@@ -278,6 +283,14 @@ def _load() -> C.CDLL:
         "te_merkle_proof_from_leaf_hashes": (i, [u8p, sz, sz, u32, u8p]),
         "te_merkle_verify_leaf_hash": (i, [u8p, u8p, u8p, sz, u64, u32]),
         "te_commit_batch_device": (i, [vp, u64, u64, u32, sz, u32, vp, vp, vp, vp]),
+        "te_roots_check_device": (i, [vp, u32, sz, u32, vp, vp, vp, vp, vp, vp]),
+        "te_verify_data_work_bytes": (sz, [vp, C.POINTER(te_object), sz]),
+        "te_verify_data_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_object), sz, u32, vp, vp,
+                                            vp, sz, vp, vp, vp, vp]),
+        "te_verify_data_batch_host": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_object), sz, u32, vp, vp, vp,
+                                          vp, vp, sz]),
+        "te_slicer_verify_data": (i, [vp, C.POINTER(te_slicer_cfg), u8p, sz, u32, u8p, u8p, C.POINTER(i)]),
+        "te_clay_verify_data_launch_stats": (i, [vp, C.POINTER(te_verify_data_stats)]),
         "te_verify_slice": (i, [u8p, u32, u32, u8p, sz]),
         "te_verify_order": (i, [C.POINTER(te_verify_item), sz, u32p]),
         "te_verify_leaves_device": (i, [vp, vp, C.POINTER(te_verify_item), sz, vp, vp, vp, vp, vp]),

@@ -74,6 +74,71 @@ def encode_commit_batch_host(slicer: Slicer, data, objs: list[tuple[int, int, in
     _check(r, "encode")
 
 
+def verify_data_work_bytes(slicer: Slicer, objs) -> int:
+    """te_verify_data_work_bytes: the device work buffer verify_data_batch needs for `objs`."""
+    arr = objs if _is_desc(objs) else encode_descs(objs)
+    return int(lib.te_verify_data_work_bytes(slicer.coder.handle, arr, len(arr)))
+
+
+def verify_data_batch(slicer: Slicer, data, objs, expected_roots, expected_leaves=None, roots=None, ok=None,
+                      bad_leaf_mask=None, work=None, height: int = SLICE_TREE_HEIGHT, window_bytes: int = 0,
+                      stream=None):
+    """verify_track_data's coded branch (sdk/src/track/read.rs:174-185) over a batch: re-encode each
+    object, hash its slices and check the root against expected_roots, the slices staying in HBM.
+    objs: (data_off, blob_len, out_off, chunk_index) per object (out_off is ignored), or
+    encode_descs(...) of them.
+
+    data a cuda tensor: te_verify_data_batch_device -- every buffer a cuda tensor (expected_roots
+    nobj*32 uint8; expected_leaves nobj*n*32 uint8 or None; roots nobj*32 uint8 or None; ok nobj int32;
+    bad_leaf_mask nobj int64 or None; work uint8, verify_data_work_bytes long), enqueued on the stream,
+    returns None.
+
+    data a host buffer (numpy array or CPU tensor, pinned for full PCIe rate):
+    te_verify_data_batch_host -- expected_roots / expected_leaves bytes or host arrays; returns
+    (ok, roots, bad_leaf_mask): a list of bools, a list of 32-byte roots and a list of ints (None
+    without expected_leaves).  Synchronous."""
+    arr = objs if _is_desc(objs) else encode_descs(objs)
+    cfg = slicer._cfg()
+    nobj = len(arr)
+    if hasattr(data, "is_cuda") and data.is_cuda:
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+        r = lib.te_verify_data_batch_device(slicer.coder.handle, C.byref(cfg), ptr(data), arr, nobj, height,
+                                            ptr(expected_roots), ptr(expected_leaves), ptr(work),
+                                            work.numel() if work is not None else 0, ptr(roots), ptr(ok),
+                                            ptr(bad_leaf_mask), _stream_ptr(stream))
+        _check_verify(r)
+        return None
+    n = slicer.coder.n()
+    xr = bytes(expected_roots)
+    if len(xr) != nobj * 32:
+        raise ValueError(f"expected_roots: {len(xr)} bytes, expected {nobj} x 32")
+    xrb = (C.c_uint8 * max(1, len(xr))).from_buffer_copy(xr or b"\0")
+    xlb = _leaf_bytes(expected_leaves, nobj, n) if expected_leaves is not None else None
+    rb = (C.c_uint8 * max(1, nobj * 32))()
+    okb = (C.c_uint32 * max(1, nobj))()
+    mb = (C.c_uint64 * max(1, nobj))() if xlb is not None else None
+    r = lib.te_verify_data_batch_host(slicer.coder.handle, C.byref(cfg), C.c_void_p(_host_ptr(data)), arr, nobj, height,
+                                      xrb, xlb, rb, okb, mb, window_bytes)
+    _check_verify(r)
+    raw = bytes(rb)
+    return ([bool(x) for x in okb[:nobj]], [raw[i * 32:(i + 1) * 32] for i in range(nobj)],
+            [int(x) for x in mb[:nobj]] if mb is not None else None)
+
+
+def _check_verify(r: int) -> None:
+    if r == _lib.TE_ERR_MERKLE_TREE_FULL:
+        raise ValueError("more slices than a tree of this height has leaves")
+    _check(r, "encode")
+
+
+def verify_data_launch_stats(coder: ClayCoder) -> dict:
+    """te_clay_verify_data_launch_stats: objects, windows, groups, launches and PCIe bytes of the
+    handle's last data-verify call."""
+    st = _lib.te_verify_data_stats()
+    _check(lib.te_clay_verify_data_launch_stats(coder.handle, C.byref(st)), "encode")
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+
 class StreamWriter:
     """te_stream_writer: the stream writer's ordered encode stage (sdk/src/stream/write.rs:332-362,
     FuturesOrdered over chunk encodes) as one GPU pipeline per handle.  submit() enqueues a window --

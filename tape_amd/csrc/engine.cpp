@@ -565,6 +565,8 @@ struct te_clay {
     HostBuf snap_host;
     DevBuf snap_in, snap_work, snap_out, snap_commit;
     te_snapshot_stats sns{};
+    // the last data-verify call (te_verify_data_batch_device / _host, te_slicer_verify_data)
+    te_verify_data_stats vds{};
 };
 
 // Drain and free everything a handle holds on its device (on that device).
@@ -802,6 +804,13 @@ int te_clay_encode_launch_stats(te_clay *c, te_encode_launch_stats *out) {
     if (!c || !out) return TE_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     *out = c->els;
+    return TE_OK;
+}
+
+int te_clay_verify_data_launch_stats(te_clay *c, te_verify_data_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->vds;
     return TE_OK;
 }
 
@@ -2588,10 +2597,11 @@ static int group_open(CommitPipe &P, OpenGroup &G, uint64_t need_out, uint64_t n
 // -- its encodes run ahead of the copies (one D2H per two encodes on a slot, the rest after the
 // group's last encode), so its hashing, the only exposed one, starts about halfway through the
 // group's copies.  `pieces` (a host-hashed group with pinned output): each large object's slices
-// are copied out in row pieces with an event per piece (copy_out_pieces).
+// are copied out in row pieces with an event per piece (copy_out_pieces).  `slices_out` false (the
+// data-verify pipeline): the slices stay in the group buffer, no D2H at all.
 static int group_add(te_clay *c, const te_slicer_cfg *cfg, CommitPipe &P, OpenGroup &G, const CommitBatch &B,
-                     const CommitPlan &L, size_t x, bool last, bool pieces = false) {
-    if (last) pieces = false;
+                     const CommitPlan &L, size_t x, bool last, bool pieces = false, bool slices_out = true) {
+    if (last || !slices_out) pieces = false;
     constexpr int S = CommitPipe::S;
     const size_t i = L.gcut[x], j = L.gcut[x + 1];
     const std::vector<size_t> &wc = L.wcut[x];
@@ -2642,11 +2652,11 @@ static int group_add(te_clay *c, const te_slicer_cfg *cfg, CommitPipe &P, OpenGr
                 seg.pieces.push_back(std::move(pe));
                 od += B.out_bytes[o];
             }
-        } else {
+        } else if (slices_out) {
             pend[k].push_back(hout);
         }
         if (rc) break;
-        if (!pieces && (!last || ++encs[k] % 2 == 0)) {
+        if (slices_out && !pieces && (!last || ++encs[k] % 2 == 0)) {
             if ((rc = copy_runs(pend[k].front(), gout, B.h_out, hipMemcpyDeviceToHost, P.ss[k]))) break;
             pend[k].pop_front();
         }
@@ -2830,6 +2840,100 @@ static int group_close(CommitPipe &P, OpenGroup &G, uint32_t n, uint32_t height,
     return TE_OK;
 }
 
+// te_verify_data_batch_host's side of a call: the expected commitments and the results, all in one
+// page-locked staging block (a copy to or from the caller's pageable arrays would make the host
+// wait for the hashing stream once per group) that the call fills before its first group and
+// empties after its last.
+struct VerifyData {
+    const uint8_t *exp_root = nullptr, *exp_leaf = nullptr;  // nobj * 32, nobj * n * 32 (or null)
+    uint8_t *root = nullptr;                                 // nobj * 32
+    uint64_t *mask = nullptr;                                // nobj (or null: not asked for)
+    uint32_t *ok = nullptr;                                  // nobj
+    te_verify_data_stats *st = nullptr;
+};
+// A verify group's rows in its commitment buffer: leaf hashes, expected leaves, expected roots,
+// observed roots, masks, verdicts -- each an array over the buffer's rows_cap rows.
+static uint64_t verify_row_bytes(uint64_t leaf_b) { return 2 * leaf_b + 2 * TE_HASH_SIZE + 8 + 4; }
+
+// group_close for the data-verify pipeline: the leaf launches per run of equal slice lengths, no
+// tree and no proofs, then one root-check launch over the group's rows and the D2H of its results
+// -- the group's only copy back.
+static int group_close_verify(CommitPipe &P, OpenGroup &G, uint32_t n, uint32_t height, uint64_t leaf_b,
+                              const VerifyData &vd) {
+    constexpr int S = CommitPipe::S;
+    if (!G.open) return TE_OK;
+    G.open = false;
+    uint8_t *gout = P.gout[G.r]->as<uint8_t>(), *dc = P.gcom[G.r]->as<uint8_t>();
+    const uint64_t cap = G.rows_cap;
+    const uint64_t xleaf_at = cap * leaf_b, xroot_at = 2 * cap * leaf_b, root_at = xroot_at + cap * TE_HASH_SIZE,
+                   mask_at = root_at + cap * TE_HASH_SIZE, ok_at = mask_at + cap * 8;
+    // the expected commitments go up while the slot streams still encode
+    for (const GroupSeg &sg : G.segs) {
+        TE_HIP(hipMemcpyAsync(dc + xroot_at + sg.row0 * TE_HASH_SIZE, vd.exp_root + sg.obj0 * TE_HASH_SIZE,
+                              sg.cnt * TE_HASH_SIZE, hipMemcpyHostToDevice, P.hs));
+        vd.st->h2d_expected_bytes += sg.cnt * TE_HASH_SIZE;
+        if (vd.exp_leaf) {
+            TE_HIP(hipMemcpyAsync(dc + xleaf_at + sg.row0 * leaf_b, vd.exp_leaf + sg.obj0 * leaf_b, sg.cnt * leaf_b,
+                                  hipMemcpyHostToDevice, P.hs));
+            vd.st->h2d_expected_bytes += sg.cnt * leaf_b;
+        }
+    }
+    for (int k = 0; k < S; k++)
+        if (G.slots_used[k]) TE_HIP(hipStreamWaitEvent(P.hs, P.ev_enc[k], 0));
+    uint64_t o = 0;
+    for (const GroupSeg &sg : G.segs) {
+        uint64_t off = sg.gout_off;
+        for (size_t q = 0; q < sg.cnt;) {
+            size_t e = q + 1;
+            uint64_t run = sg.out_bytes[q];
+            while (e < sg.cnt && sg.slice_len[e] == sg.slice_len[q]) run += sg.out_bytes[e++];
+            CommitArgs ca{};
+            ca.slices = gout + off;
+            ca.obj_stride = sg.out_bytes[q];
+            ca.slice_len = sg.slice_len[q];
+            ca.n = n;
+            ca.nobj = (uint32_t)(e - q);
+            ca.height = height;
+            ca.leaf = dc + o * leaf_b;
+            TE_HIP(launch_commit(ca, P.hs));
+            vd.st->leaf_launches += commit_leaf_launches(ca.slice_len);
+            o += e - q;
+            off += run;
+            q = e;
+        }
+    }
+    RootCheckArgs ra{};
+    ra.leaf = dc;
+    ra.expected_root = dc + xroot_at;
+    ra.expected_leaf = vd.exp_leaf ? dc + xleaf_at : nullptr;
+    ra.root = dc + root_at;
+    ra.ok = reinterpret_cast<uint32_t *>(dc + ok_at);
+    ra.bad_leaf_mask = vd.exp_leaf && vd.mask ? reinterpret_cast<uint64_t *>(dc + mask_at) : nullptr;
+    ra.nobj = G.rows;
+    ra.n = n;
+    ra.height = height;
+    TE_HIP(launch_root_check(ra, P.hs));
+    vd.st->root_check_launches++;
+    for (const GroupSeg &sg : G.segs) {
+        const struct { void *h; uint64_t d, len; } back[3] = {
+            {vd.root ? vd.root + sg.obj0 * TE_HASH_SIZE : nullptr, root_at + sg.row0 * TE_HASH_SIZE, sg.cnt * TE_HASH_SIZE},
+            {vd.ok + sg.obj0, ok_at + sg.row0 * 4, sg.cnt * 4},
+            {ra.bad_leaf_mask ? vd.mask + sg.obj0 : nullptr, mask_at + sg.row0 * 8, sg.cnt * 8}};
+        for (const auto &bk : back)
+            if (bk.h && bk.len) {
+                TE_HIP(hipMemcpyAsync(bk.h, dc + bk.d, bk.len, hipMemcpyDeviceToHost, P.hs));
+                vd.st->d2h_bytes += bk.len;
+            }
+    }
+    for (int k = 0; k < S; k++)
+        if (G.slots_used[k]) TE_HIP(hipStreamWaitEvent(P.hs, P.ev_slot[k], 0));
+    TE_HIP(hipEventRecord(P.ev_hashed[G.r], P.hs));
+    P.hashed_pending[G.r] = true;
+    P.groups++;
+    G.segs.clear();
+    return TE_OK;
+}
+
 // Who hashes a group (te_set_commit_hashing / te_stream_writer_set_hashing, TE_HASH_*).  A leaf
 // launch hashes one slice per lane at ~24 MB/s per lane (715,048 B in ~29.5 ms)
 // whatever the number of slices up to ~64k of them; the host pool hashes at its measured
@@ -2904,8 +3008,10 @@ static int commit_streams(te_clay *c, hipStream_t ss[2], hipStream_t &hs) {
 
 static int encode_commit_host_impl(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_data,
                                    const te_object *objs, size_t nobj, uint8_t *h_out, size_t group_bytes,
-                                   const CommitOut &co) {
-    if (!c || !cfg || (!objs && nobj) || (nobj && (!h_data || !h_out))) return TE_ERR_INVALID_ARG;
+                                   const CommitOut &co, const VerifyData *vd = nullptr) {
+    // vd set: the data-verify form -- the same plan, streams and buffers; no h_out, the slices stay
+    // in the group buffers, every group hashed on the device and closed by group_close_verify
+    if (!c || !cfg || (!objs && nobj) || (nobj && (!h_data || (!h_out && !vd)))) return TE_ERR_INVALID_ARG;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
     if (group_bytes == 0) group_bytes = (size_t)4 << 30;
     const uint64_t copy_bytes = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)128 << 20, group_bytes / 8));
@@ -2919,9 +3025,12 @@ static int encode_commit_host_impl(te_clay *c, const te_slicer_cfg *cfg, const u
     if (rc) return rc;
     CommitPlan L;
     commit_plan(B, group_bytes, copy_bytes, L);
-    const uint64_t commit_cap = L.max_group_obj * (B.leaf_b + TE_HASH_SIZE + B.proof_b);
+    const uint64_t row_b = vd ? verify_row_bytes(B.leaf_b) : B.leaf_b + TE_HASH_SIZE + B.proof_b;
+    const uint64_t commit_cap = L.max_group_obj * row_b;
 
-    std::lock_guard<std::mutex> lk(c->mu);
+    // (a verify call holds the handle's lock already: it stages its commitments under it)
+    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    if (!vd) lk.lock();
     c->els = te_encode_launch_stats{};
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
@@ -2946,8 +3055,13 @@ static int encode_commit_host_impl(te_clay *c, const te_slicer_cfg *cfg, const u
         TE_HIP(P.gcom[r]->ensure(commit_cap));
     }
     rc = P.make_events();
-    const uint64_t row_b = B.leaf_b + TE_HASH_SIZE + B.proof_b;
-    const bool pinned_out = host_pinned(h_out);
+    const bool pinned_out = !vd && host_pinned(h_out);
+    if (vd) {
+        vd->st->objects = nobj;
+        vd->st->groups = L.gcut.size() - 1;
+        for (const auto &wc : L.wcut) vd->st->windows += wc.size() - 1;
+        for (size_t o = 0; o < nobj; o++) vd->st->h2d_bytes += objs[o].blob_len;
+    }
     OpenGroup G;
     std::vector<std::shared_ptr<hh::Job>> jobs;
     for (size_t x = 0; x < ngroups && rc == TE_OK; x++) {
@@ -2955,7 +3069,7 @@ static int encode_commit_host_impl(te_clay *c, const te_slicer_cfg *cfg, const u
         group_need(B, L, x, need_out, need_rows);
         uint64_t max_slice = 0;
         for (size_t o = L.gcut[x]; o < L.gcut[x + 1]; o++) max_slice = std::max<uint64_t>(max_slice, B.slice_len[o]);
-        const bool host = host_hash_wins(g_commit_hashing.load(), need_rows * B.n, max_slice, need_out);
+        const bool host = !vd && host_hash_wins(g_commit_hashing.load(), need_rows * B.n, max_slice, need_out);
         static const bool trace = tec_knob("TEC_COMMIT_TRACE") != nullptr;  // measurement: the choice per group
         if (trace)
             fprintf(stderr, "[tapeec] commit group %zu/%zu: %llu objects, %llu slice bytes, %s hashing (pool %.2f GB/s x %d)\n",
@@ -2964,9 +3078,11 @@ static int encode_commit_host_impl(te_clay *c, const te_slicer_cfg *cfg, const u
         const auto t0 = std::chrono::steady_clock::now();
         rc = group_open(P, G, need_out, need_rows, row_b);
         const auto t1 = std::chrono::steady_clock::now();
-        if (!rc) rc = group_add(c, cfg, P, G, B, L, x, x + 1 == ngroups && !host, host && pinned_out);
+        if (!rc) rc = group_add(c, cfg, P, G, B, L, x, x + 1 == ngroups && !host, host && pinned_out, !vd);
         const auto t2 = std::chrono::steady_clock::now();
-        if (!rc && host) {
+        if (!rc && vd) {
+            rc = group_close_verify(P, G, B.n, B.co.height, B.leaf_b, *vd);
+        } else if (!rc && host) {
             jobs.emplace_back();
             rc = group_close_host(P, G, B.n, B.co.height, c->device, jobs.back());
         } else if (!rc) {
@@ -4479,6 +4595,239 @@ int te_commit_batch_device(const uint8_t *d_slices, uint64_t obj_stride, uint64_
     KTimer kt(s);
     TE_HIP(launch_commit(a, s));
     kt.stop();
+    return TE_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Data verify (root_check.hip): verify_track_data's coded branch (sdk/src/track/read.rs:174-185)
+// -- BlobEncoder::encode_with_root (sdk/src/codec/encoder.rs:166-193) and the compare with
+// blob.commitment -- with the slices kept in HBM
+// ------------------------------------------------------------------------------------------
+namespace {
+
+// the tree arguments every data-verify entry point shares, checked before any device call
+int verify_data_tree_args(const te_clay *c, uint32_t height) {
+    if (height == 0 || height > TE_MAX_MERKLE_TREE_HEIGHT) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n;
+    if (n > TE_COMMIT_MAX_LEAVES) return TE_ERR_INVALID_ARG;
+    if ((uint64_t)n > (1ull << height)) return TE_ERR_MERKLE_TREE_FULL;
+    return TE_OK;
+}
+
+// The device batch's work buffer: the objects' slices back to back (each n * slice_len, a multiple
+// of 4), padded to 32 bytes, then nobj * n leaf hashes.
+struct VerifyWork {
+    std::vector<te_object> local;       // the encode's descriptors: out_off = the slices' place
+    std::vector<uint64_t> slice_len;
+    uint64_t leaf_at = 0, bytes = 0;
+};
+int verify_work_layout(const te_clay *c, const te_object *objs, size_t nobj, VerifyWork &W) {
+    const uint64_t n = (uint64_t)c->h.n;
+    W.local.resize(nobj);
+    W.slice_len.resize(nobj);
+    uint64_t at = 0;
+    for (size_t o = 0; o < nobj; o++) {
+        te_geometry g;
+        te_slicer_geometry(c, objs[o].blob_len, &g);
+        if (g.slice_len % 4) return TE_ERR_INVALID_ARG;  // the leaf kernel reads dwords
+        W.local[o] = te_object{objs[o].data_off, objs[o].blob_len, at, objs[o].chunk_index};
+        W.slice_len[o] = g.slice_len;
+        at += n * g.slice_len;
+    }
+    W.leaf_at = (at + 31) & ~(uint64_t)31;
+    W.bytes = W.leaf_at + (uint64_t)nobj * n * TE_HASH_SIZE;
+    return TE_OK;
+}
+
+// Encode into d_work, hash each run of equal slice lengths, root-check every object: all enqueued
+// on s (handle locked, its device current).
+int verify_data_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, const VerifyWork &W,
+                        uint32_t height, const uint8_t *d_expected_roots, const uint8_t *d_expected_leaves,
+                        uint8_t *d_work, uint8_t *d_roots, uint32_t *d_ok, uint64_t *d_bad_leaf_mask, hipStream_t s,
+                        bool per_call) {
+    const size_t nobj = W.local.size();
+    const uint32_t n = (uint32_t)c->h.n;
+    const uint64_t leaf_b = (uint64_t)n * TE_HASH_SIZE;
+    int r = encode_enqueue(c, cfg, d_data, W.local.data(), nobj, d_work, s, false, nullptr, StripeSel(), per_call);
+    if (r) return r;
+    KTimer kt(s);
+    for (size_t o = 0; o < nobj;) {
+        size_t e = o + 1;
+        while (e < nobj && W.slice_len[e] == W.slice_len[o]) e++;
+        CommitArgs ca{};
+        ca.slices = d_work + W.local[o].out_off;
+        ca.obj_stride = (uint64_t)n * W.slice_len[o];
+        ca.slice_len = W.slice_len[o];
+        ca.n = n;
+        ca.nobj = (uint32_t)(e - o);
+        ca.height = height;
+        ca.leaf = d_work + W.leaf_at + o * leaf_b;
+        TE_HIP(launch_commit(ca, s));
+        c->vds.groups++;
+        c->vds.leaf_launches += commit_leaf_launches(ca.slice_len);
+        o = e;
+    }
+    RootCheckArgs ra{};
+    ra.leaf = d_work + W.leaf_at;
+    ra.expected_root = d_expected_roots;
+    ra.expected_leaf = d_expected_leaves;
+    ra.root = d_roots;
+    ra.ok = d_ok;
+    ra.bad_leaf_mask = d_bad_leaf_mask;
+    ra.nobj = nobj;
+    ra.n = n;
+    ra.height = height;
+    TE_HIP(launch_root_check(ra, s));
+    kt.stop();
+    c->vds.objects = nobj;
+    c->vds.windows = 1;
+    c->vds.root_check_launches = 1;
+    return TE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int te_roots_check_device(const uint8_t *d_leaf_hashes, uint32_t n, size_t nobj, uint32_t height,
+                          const uint8_t *d_expected_roots, const uint8_t *d_expected_leaves, uint8_t *d_roots,
+                          uint32_t *d_ok, uint64_t *d_bad_leaf_mask, void *stream) {
+    auto odd = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; };
+    if (n == 0 || n > TE_COMMIT_MAX_LEAVES || height > TE_MAX_MERKLE_TREE_HEIGHT || (uint64_t)n > (1ull << height) ||
+        !d_leaf_hashes || !d_expected_roots || !d_ok || nobj > 0xffffffffull / n || odd(d_leaf_hashes) ||
+        odd(d_expected_roots) || odd(d_expected_leaves) || odd(d_roots) || odd(d_ok) ||
+        (reinterpret_cast<uintptr_t>(d_bad_leaf_mask) & 7u))
+        return TE_ERR_INVALID_ARG;
+    if (nobj == 0) return TE_OK;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    RootCheckArgs a{};
+    a.leaf = d_leaf_hashes;
+    a.expected_root = d_expected_roots;
+    a.expected_leaf = d_expected_leaves;
+    a.root = d_roots;
+    a.ok = d_ok;
+    a.bad_leaf_mask = d_bad_leaf_mask;
+    a.nobj = nobj;
+    a.n = n;
+    a.height = height;
+    hipStream_t s = (hipStream_t)stream;
+    KTimer kt(s);
+    TE_HIP(launch_root_check(a, s));
+    kt.stop();
+    return TE_OK;
+}
+
+size_t te_verify_data_work_bytes(const te_clay *c, const te_object *objs, size_t nobj) {
+    if (!c || (!objs && nobj)) return 0;
+    VerifyWork W;
+    if (verify_work_layout(c, objs, nobj, W)) return 0;
+    return (size_t)W.bytes;
+}
+
+int te_verify_data_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, const te_object *objs,
+                                size_t nobj, uint32_t height, const uint8_t *d_expected_roots,
+                                const uint8_t *d_expected_leaves, uint8_t *d_work, size_t work_bytes, uint8_t *d_roots,
+                                uint32_t *d_ok, uint64_t *d_bad_leaf_mask, void *stream) {
+    if (!c || !cfg || (!objs && nobj) || (nobj && (!d_data || !d_expected_roots || !d_work || !d_ok)))
+        return TE_ERR_INVALID_ARG;
+    if (int r = verify_data_tree_args(c, height)) return r;
+    if ((reinterpret_cast<uintptr_t>(d_work) & 15u) || nobj > 0xffffffffull / (size_t)c->h.n) return TE_ERR_INVALID_ARG;
+    VerifyWork W;
+    if (int r = verify_work_layout(c, objs, nobj, W)) return r;
+    if (work_bytes < W.bytes) return TE_ERR_BUFFER_TOO_SMALL;
+    if (nobj == 0) return TE_OK;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->els = te_encode_launch_stats{};
+    c->vds = te_verify_data_stats{};
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    return verify_data_enqueue(c, cfg, d_data, W, height, d_expected_roots, d_expected_leaves, d_work, d_roots, d_ok,
+                               d_bad_leaf_mask, (hipStream_t)stream, false);
+}
+
+int te_verify_data_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_data, const te_object *objs,
+                              size_t nobj, uint32_t height, const uint8_t *h_expected_roots,
+                              const uint8_t *h_expected_leaves, uint8_t *h_roots, uint32_t *h_ok,
+                              uint64_t *h_bad_leaf_mask, size_t window_bytes) {
+    if (!c || !cfg || (!objs && nobj) || (nobj && (!h_data || !h_expected_roots || !h_ok))) return TE_ERR_INVALID_ARG;
+    if (int r = verify_data_tree_args(c, height)) return r;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    const uint64_t leaf_b = (uint64_t)c->h.n * TE_HASH_SIZE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->vds = te_verify_data_stats{};
+    if (nobj == 0) return TE_OK;
+    // the page-locked staging block: expected roots, expected leaves | roots, masks, verdicts
+    const uint64_t xleaf_at = nobj * TE_HASH_SIZE, root_at = xleaf_at + (h_expected_leaves ? nobj * leaf_b : 0),
+                   mask_at = root_at + nobj * TE_HASH_SIZE, ok_at = mask_at + nobj * 8, total = ok_at + nobj * 4;
+    {
+        DeviceGuard dg(c->device);
+        TE_HIP(dg.err);
+        TE_HIP(c->ver_host.ensure(total));
+    }
+    uint8_t *st = c->ver_host.u8();
+    memcpy(st, h_expected_roots, nobj * TE_HASH_SIZE);
+    if (h_expected_leaves) memcpy(st + xleaf_at, h_expected_leaves, nobj * leaf_b);
+    VerifyData vd;
+    vd.exp_root = st;
+    vd.exp_leaf = h_expected_leaves ? st + xleaf_at : nullptr;
+    vd.root = h_roots ? st + root_at : nullptr;
+    vd.mask = h_bad_leaf_mask ? reinterpret_cast<uint64_t *>(st + mask_at) : nullptr;
+    vd.ok = reinterpret_cast<uint32_t *>(st + ok_at);
+    vd.st = &c->vds;
+    const CommitOut co{nullptr, nullptr, nullptr, height};
+    // default group 8 GiB: a group costs one slice's SHA-256 chain (~30 ms at 4 MiB objects) whatever
+    // it holds and nothing is copied out meanwhile, so fewer groups are faster -- 1024 x 4 MiB: 532 ms
+    // at 1 GiB (18 groups), 166 at 4 GiB (5), 137 at 8 GiB (3), 115 in one group;
+    // 8 GiB keeps the three resident group buffers at 6.3 GB each
+    if (window_bytes == 0) window_bytes = (size_t)8 << 30;
+    const int rc = encode_commit_host_impl(c, cfg, h_data, objs, nobj, nullptr, window_bytes, co, &vd);
+    if (rc) return rc;
+    if (h_roots) memcpy(h_roots, st + root_at, nobj * TE_HASH_SIZE);
+    if (h_bad_leaf_mask && h_expected_leaves) memcpy(h_bad_leaf_mask, st + mask_at, nobj * 8);
+    memcpy(h_ok, st + ok_at, nobj * 4);
+    return TE_OK;
+}
+
+int te_slicer_verify_data(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *data, size_t len, uint32_t height,
+                          const uint8_t expected_root[TE_HASH_SIZE], uint8_t observed_root[TE_HASH_SIZE], int *ok) {
+    if (!c || !cfg || (!data && len) || !expected_root || !ok) return TE_ERR_INVALID_ARG;
+    if (int r = verify_data_tree_args(c, height)) return r;
+    const te_object obj{0, len, 0, cfg->chunk_index};
+    VerifyWork W;
+    if (int r = verify_work_layout(c, &obj, 1, W)) return r;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->els = te_encode_launch_stats{};
+    c->vds = te_verify_data_stats{};
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    int r = ensure_stream(c);
+    if (r) return r;
+    // the handle's staging: the object in io_in, the work buffer in io_out with the expected root,
+    // the observed root and the verdict behind it; their host side in ver_host
+    const uint64_t xroot_at = (W.bytes + 31) & ~(uint64_t)31, root_at = xroot_at + TE_HASH_SIZE, ok_at = root_at + TE_HASH_SIZE;
+    TE_HIP(c->io_in.ensure(len + 16));
+    TE_HIP(c->io_out.ensure(ok_at + 4));
+    TE_HIP(c->ver_host.ensure(2 * TE_HASH_SIZE + 4));
+    uint8_t *hst = c->ver_host.u8(), *dw = c->io_out.as<uint8_t>();
+    memcpy(hst, expected_root, TE_HASH_SIZE);
+    if (len) TE_HIP(hipMemcpyAsync(c->io_in.p, data, len, hipMemcpyHostToDevice, c->stream));
+    TE_HIP(hipMemcpyAsync(dw + xroot_at, hst, TE_HASH_SIZE, hipMemcpyHostToDevice, c->stream));
+    r = verify_data_enqueue(c, cfg, c->io_in.as<uint8_t>(), W, height, dw + xroot_at, nullptr, dw, dw + root_at,
+                            reinterpret_cast<uint32_t *>(dw + ok_at), nullptr, c->stream, true);
+    if (r) return r;
+    TE_HIP(hipMemcpyAsync(hst + TE_HASH_SIZE, dw + root_at, TE_HASH_SIZE + 4, hipMemcpyDeviceToHost, c->stream));
+    TE_HIP(hipStreamSynchronize(c->stream));
+    c->vds.h2d_bytes = len;
+    c->vds.h2d_expected_bytes = TE_HASH_SIZE;
+    c->vds.d2h_bytes = TE_HASH_SIZE + 4;
+    if (observed_root) memcpy(observed_root, hst + TE_HASH_SIZE, TE_HASH_SIZE);
+    uint32_t v;
+    memcpy(&v, hst + 2 * TE_HASH_SIZE, 4);
+    *ok = v ? 1 : 0;
     return TE_OK;
 }
 

@@ -317,6 +317,27 @@ struct CommitArgs {
 };
 hipError_t launch_commit(const CommitArgs &a, hipStream_t s);
 
+// ---- root and check of an object from its leaf hashes (root_check.hip) ----
+constexpr int kRootCheckWaves = 4;    // objects (waves) per workgroup
+constexpr int kRootCheckLevels = 33;  // EMPTY_ROOTS[0 .. 32] (tree.rs:15-48)
+struct RootCheckArgs {
+    const uint8_t *leaf;           // object o's n leaf hashes at leaf + o * n * 32
+    const uint8_t *expected_root;  // nobj * 32
+    const uint8_t *expected_leaf;  // nobj * n * 32, or null
+    uint8_t *root;                 // nobj * 32: the observed roots, or null
+    uint32_t *ok;                  // nobj: observed root == expected root
+    uint64_t *bad_leaf_mask;       // nobj, or null: bit i = leaf i != expected leaf i (expected_leaf set)
+    uint64_t nobj;
+    uint32_t n, height;            // n <= kCommitMaxLeaves, height <= 32, n <= 2^height
+    uint32_t empty[kRootCheckLevels][8];  // EMPTY_ROOTS as big-endian words; the launcher fills it
+};
+hipError_t launch_root_check(RootCheckArgs a, hipStream_t s);
+// leaf_kernel launches of one launch_commit call for slices of slice_len bytes
+inline uint64_t commit_leaf_launches(uint64_t slice_len) {
+    const uint64_t T = (slice_len + 4u + 8u) / 64u + 1u, nl = (T + 1535u) / 1536u, per = (T + nl - 1) / nl;
+    return (T + per - 1) / per;
+}
+
 // ---- leaf verification (verify.hip) ----
 // One slice to hash and check, in the order the kernel walks them: sorted by block count,
 // descending.  `index` is the item's position in the caller's list; digests and ok are stored there.

@@ -163,6 +163,20 @@ def commit_batch(slices, obj_stride: int, slice_len: int, n: int, nobj: int, lea
     _check(r)
 
 
+def roots_check_device(leaf_hashes, n: int, nobj: int, expected_roots, ok, expected_leaves=None, roots=None,
+                       bad_leaf_mask=None, height: int = SLICE_TREE_HEIGHT, stream=None) -> None:
+    """te_roots_check_device: root_from_leaf_hashes::<height> of nobj objects' n leaf hashes, checked
+    against expected roots on the device (the compare of verify_track_data, sdk/src/track/read.rs:
+    174-185).  cuda tensors: leaf_hashes nobj*n*32 uint8, expected_roots nobj*32 uint8, ok nobj int32
+    (1 = roots equal); optional expected_leaves nobj*n*32 uint8, roots nobj*32 uint8 (observed),
+    bad_leaf_mask nobj int64 (bit i = leaf i differs; written only with expected_leaves).  Enqueued
+    on the stream."""
+    from .batch import _stream_ptr
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)  # noqa: E731
+    _check(lib.te_roots_check_device(ptr(leaf_hashes), n, nobj, height, ptr(expected_roots), ptr(expected_leaves),
+                                     ptr(roots), ptr(ok), ptr(bad_leaf_mask), _stream_ptr(stream)))
+
+
 def commit_slices(slices, height: int = SLICE_TREE_HEIGHT):
     """encode_with_proofs' commitment (encoder.rs:226-234) of one object's slices on the device:
     (leaf hashes, root, proofs)."""

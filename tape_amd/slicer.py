@@ -578,6 +578,38 @@ class Slicer:
         sl = g.slice_len
         return [raw[i * sl:(i + 1) * sl] for i in range(n)]
 
+    def _verify_data(self, data: bytes, expected: bytes, chunk_index: int, height: int) -> tuple[bool, bytes]:
+        if len(expected) != 32:
+            raise ValueError("a commitment is 32 bytes")
+        cfg = self._cfg()
+        cfg.chunk_index = chunk_index
+        root = (C.c_uint8 * 32)()
+        ok = C.c_int()
+        r = lib.te_slicer_verify_data(self.coder.handle, C.byref(cfg), _buf(data), len(data), height,
+                                      (C.c_uint8 * 32).from_buffer_copy(expected), root, C.byref(ok))
+        if r == _lib.TE_ERR_MERKLE_TREE_FULL:
+            raise ValueError("more slices than a tree of this height has leaves")
+        _check(r, "encode")
+        return ok.value == 1, bytes(root)
+
+    def encode_root(self, data: bytes, chunk_index: int = 0, height: int = SLICE_TREE_HEIGHT) -> bytes:
+        """The root of BlobEncoder::encode_with_root (sdk/src/codec/encoder.rs:166-193): Slicer::encode,
+        hash_leaf per slice, root_from_leaf_hashes -- on the device, the slices never leave it."""
+        return self._verify_data(data, bytes(32), chunk_index, height)[1]
+
+    def verify_data(self, data: bytes, commitment: bytes, chunk_index: int = 0,
+                    height: int = SLICE_TREE_HEIGHT) -> bool:
+        """verify_track_data's coded branch (sdk/src/track/read.rs:174-185): re-encode `data` and
+        compare the root with the on-chain commitment (te_slicer_verify_data)."""
+        return self._verify_data(data, bytes(commitment), chunk_index, height)[0]
+
+    def verify_data_launch_stats(self) -> dict:
+        """te_clay_verify_data_launch_stats: objects, windows, groups, launches and PCIe bytes of the
+        handle's last data-verify call."""
+        st = _lib.te_verify_data_stats()
+        _check(lib.te_clay_verify_data_launch_stats(self.coder.handle, C.byref(st)), "encode")
+        return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
     def decode(self, chunks: list[tuple[int, bytes]]) -> bytes:
         """Slicer::decode (slicer.rs:298-364)."""
         if not chunks:
