@@ -25,7 +25,14 @@ sc & 15 in both.  The Clay(20,7,16) sub-chunk sizes below give, as (sc & 15: sc)
   last workgroup, < 16   2: 1538 3074   4: 1540   14: 3086
 260, 518, 776, 1034, 1276, 10, 12 and the eight between 1540 and 3086 supply the tails the other
 sizes leave out (test_tail_coverage checks this table against the lists).  The largest inputs are
-2.2 MB (K = 7, sc = 3086) and 1.5 MB (K = 10, sc = 1538)."""
+2.2 MB (K = 7, sc = 3086) and 1.5 MB (K = 10, sc = 1538).
+
+Row stores of the LDS-DMA kernel (encode_dma.hip): one workgroup stores whole rows, nb = sc >> 4
+16-byte blocks on lanes 0..63 and, as a second store, 64..nb - 1, then for tail = sc & 15 != 0 the
+lane with lane + 64 == nb rewriting the row's last 16 bytes.  Its sizes, at both ends of its range
+1282..1440, as (sc & 15: sc); nb = 80 up to 1294, 89 from 1428 and 90 at 1440:
+  LDS-DMA, whole row     0: 1440   2: 1282   4: 1284 1428   6: 1430   8: 1288 1432   10: 1290 1434
+                         12: 1292 1436   14: 1294 1438"""
 import ctypes as C
 import functools
 
@@ -48,7 +55,7 @@ STAGE_7 = {2: (1, 1), 4: (1, 1), 6: (1, 1), 8: (1, 1), 10: (1, 1), 12: (1, 1), 1
            1796: (6, 2), 1798: (6, 2), 2056: (6, 2), 2314: (6, 2), 2572: (6, 2), 2830: (6, 2), 3072: (6, 2),
            3074: (6, 3), 3086: (6, 3)}
 STAGE_10 = {8: (1, 1), 256: (1, 1), 258: (2, 1), 770: (4, 1), 1026: (5, 1), 1282: (6, 1), 1430: (6, 1), 1538: (6, 2)}
-DMA_7 = (1282, 1430, 1440)
+DMA_7 = (1282, 1284, 1288, 1290, 1292, 1294, 1428, 1430, 1432, 1434, 1436, 1438, 1440)
 GENERIC = (((20, 8, 17), 64), ((12, 8, 11), 64))
 SHORTEN = (0, 1, 4, 1399)  # data end dword aligned, unaligned, aligned, unaligned and inside an earlier row
 
@@ -58,7 +65,8 @@ RAW_CASES = [((20, 7, 16), sc, "stage") for sc in STAGE_7] + [((20, 7, 16), sc, 
 
 def test_tail_coverage():
     """The docstring's table: every even lseg & 15 on a whole-row segment and on a last-workgroup
-    segment, as a wide tail; the short rows; and the (G, workgroups) column of STAGE_7 / STAGE_10."""
+    segment, as a wide tail; the short rows; the (G, workgroups) column of STAGE_7 / STAGE_10; and
+    every even sc & 15 on the LDS-DMA kernel's rows, with the fewest and the most 16-byte blocks."""
     whole = {sc for sc in STAGE_7 if sc <= 1536}
     last = {sc: sc - 1536 * (STAGE_7[sc][1] - 1) for sc in STAGE_7 if sc > 1536}
     assert {sc & 15 for sc in whole if sc >= 16} == set(range(0, 16, 2))
@@ -71,6 +79,10 @@ def test_tail_coverage():
             groups = -(-(-(-sc // 4)) // 64)
             assert g == min(groups, 6) and wgs == -(-groups // g), sc
     assert {g for g, _ in STAGE_7.values()} == {1, 2, 3, 4, 5, 6}
+    assert all(1280 < sc <= 1440 and sc % 2 == 0 for sc in DMA_7)
+    assert {sc & 15 for sc in DMA_7} == set(range(0, 16, 2))
+    assert {80, 90} <= {sc >> 4 for sc in DMA_7}
+    assert {sc % 4 for sc in DMA_7} == {0, 2}
 
 
 @functools.lru_cache(None)
