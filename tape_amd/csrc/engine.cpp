@@ -31,6 +31,7 @@
 #include "copy_pool.hpp"
 #include "win_plan.hpp"
 #include "dec_class.hpp"
+#include "dec_plan.hpp"
 
 using namespace tec;
 
@@ -878,15 +879,11 @@ size_t te_num_stripes(size_t blob_len, size_t stripe) {
 }
 
 uint32_t te_shard_to_slice(int rotated, uint32_t n, uint32_t stripe, uint32_t shard) {
-    if (!rotated || n == 0) return shard;
-    const uint32_t off = (uint32_t)(((uint64_t)stripe * TE_ROTATION_STEP) % n);
-    return (shard + off) % n;
+    return shard_to_slice(rotated, n, stripe, shard);
 }
 
 uint32_t te_slice_to_shard(int rotated, uint32_t n, uint32_t stripe, uint32_t slice) {
-    if (!rotated || n == 0) return slice;
-    const uint32_t off = (uint32_t)(((uint64_t)stripe * TE_ROTATION_STEP) % n);
-    return (slice + n - off) % n;
+    return slice_to_shard(rotated, n, stripe, slice);
 }
 
 void te_slice_metadata_to_bytes(const te_slice_metadata *m, uint8_t out[TE_META_SIZE]) {
@@ -1182,81 +1179,13 @@ int encode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_data, 
 // ------------------------------------------------------------------------------------------
 namespace {
 
-struct DecItem {          // one object, host-validated
-    uint64_t in_base;     // offset in d_slices of slice 0
-    uint64_t slice_len, blob_len, stripe, ns, cs, out_off;
-    uint32_t avail;
-    int32_t lost = -1;    // >= 0: output = that slice's chunks at out_off + stripe * cs (node recover)
-    // ranged read: only object bytes [w_start, w_start + w_len) are written, at out_off
-    bool ranged = false;
-    uint64_t w_start = 0, w_len = 0;
-    uint64_t in_skew = 0;  // the slices at in_base start at slice byte in_skew (te_slicer_decode_range's staging)
-    // ranged read: a stripe whose window holds exactly one erased data chunk rebuilds that chunk
-    // alone (TE_RANGE_CHUNK: the handle's knob, and range_chunk_ok of the object)
-    bool chunk = false;
-};
-
-// Ranged reads (te_slicer_range_plan): the stripes a window touches, [sb, se)
-inline void range_stripes(uint64_t S, uint64_t start, uint64_t len, uint64_t &sb, uint64_t &se) {
-    sb = se = 0;
-    if (len == 0 || S == 0) return;
-    sb = start / S;
-    se = (start + len - 1) / S + 1;
-}
-// ... and the window inside stripe st, [lo, hi) in stripe bytes.  copy: every data chunk it
-// intersects (chunk x = stripe bytes [x cs, (x + 1) cs), shard x) is a present slice's -- decided
-// from the mask itself, not from the padded erasure set -- so nothing needs decoding.
-// miss: the absent chunks among them, and the last one (the only one when miss == 1).
-struct RangeWin { uint64_t lo, hi; bool copy; uint32_t miss = 0, miss_x = 0; };
-RangeWin range_window(int n, int rotated, uint32_t avail, uint64_t blob_len, uint64_t S, uint64_t cs, uint64_t st,
-                      uint64_t start, uint64_t len) {
-    const uint64_t base = st * S, end = std::min({start + len, base + S, blob_len});
-    RangeWin w;
-    w.lo = start > base ? start - base : 0;
-    w.hi = end - base;
-    w.copy = true;
-    for (uint64_t x = w.lo / cs; x * cs < w.hi; x++)
-        if (!((avail >> te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)x)) & 1u)) {
-            w.copy = false;
-            w.miss++;
-            w.miss_x = (uint32_t)x;
-        }
-    return w;
-}
 // The chunk path (TE_RANGE_CHUNK) is open to an object where a node recover of its stripes runs a
 // class kernel: Clay(20,7,16), the class kernels not switched off (measurement knob), sub-chunks
-// of >= 8 bytes and 31-bit slice / share offsets (decode_enqueue's staged_group, on the object's
-// own slice length).  Host only: te_slicer_range_plan_ex answers from the same rule.
+// of >= 8 bytes and 31-bit slice / share offsets (dec_geom_staged, on the object's own slice
+// length).  Host only: te_slicer_range_plan_ex answers from the same rule.
 bool range_chunk_ok(const ClayHost &h, uint64_t cs, uint64_t slice_len) {
-    static const bool class_on = [] {
-        const char *e = tec_knob("TEC_DEC_CLASS");
-        return !(e && e[0] == '0');
-    }();
-    if (!class_on || h.n != kDecClassN || h.k != kDecClassK || h.q != kRepQ || h.t != 2 || h.nu != 0) return false;
-    return cs / (uint64_t)h.alpha >= 8 && (uint64_t)h.n * slice_len < 0x7fffffffull && cs * (uint64_t)h.k < 0x7fffffffull;
-}
-inline bool range_is_chunk(const DecItem &it, const RangeWin &w) { return it.chunk && w.miss == 1; }
-// every touched stripe's window, stripe sb + i at [i]
-std::vector<RangeWin> range_windows(int n, int rotated, uint32_t avail, uint64_t blob_len, uint64_t S, uint64_t cs,
-                                    uint64_t start, uint64_t len) {
-    uint64_t sb, se;
-    range_stripes(S, start, len, sb, se);
-    std::vector<RangeWin> w;
-    for (uint64_t st = sb; st < se; st++) w.push_back(range_window(n, rotated, avail, blob_len, S, cs, st, start, len));
-    return w;
-}
-// The padded erasure set of stripe st as internal nodes: the shards whose slices are missing,
-// padded to n - k erasures (the decode then reads exactly the k nodes left).
-uint64_t stripe_emask(const ClayHost &h, int rotated, uint32_t avail, uint64_t st) {
-    uint64_t emask = 0;
-    for (int sh = 0; sh < h.n; sh++)
-        if (!((avail >> te_shard_to_slice(rotated, (uint32_t)h.n, (uint32_t)st, (uint32_t)sh)) & 1u))
-            emask |= 1ull << h.ext_to_int(sh);
-    return h.pad_erasures(emask);
-}
-// check a window against the object (the argument rules of the ranged entry points)
-inline bool range_valid(uint64_t blob_len, uint64_t start, uint64_t len) {
-    return start + len >= start && start + len <= blob_len;
+    if (!dec_class_on() || h.n != kDecClassN || h.k != kDecClassK || h.q != kRepQ || h.t != 2 || h.nu != 0) return false;
+    return dec_geom_staged(h, cs, slice_len);
 }
 
 // Validate one object like Slicer::decode (slicer.rs:298-331, validate_layout :79-105).
@@ -1286,7 +1215,6 @@ int decode_validate(const te_clay *c, const uint8_t *meta48, uint64_t slice_len,
     return TE_OK;
 }
 
-// The compiled form of one padded erasure pattern, built once per handle (caller holds c->mu).
 // Compile one padded erasure pattern (host only, thread-safe: pure ClayHost work).  out_node >= 0:
 // the program outputs that internal node's chunk (ClayHost::dec_prog).
 bool compile_pattern(const ClayHost &h, uint64_t emask, int out_node, te_clay::DecCache &d) {
@@ -1329,24 +1257,21 @@ bool compile_pattern(const ClayHost &h, uint64_t emask, int out_node, te_clay::D
     return true;
 }
 
-inline uint64_t dec_key(uint64_t emask, int out_node) { return emask | (uint64_t)(out_node + 1) << 48; }
-
-// The compiled form of one padded erasure pattern, built once per handle (caller holds c->mu).
-const te_clay::DecCache *dec_pattern(te_clay *c, uint64_t emask, int out_node = -1) {
-    const uint64_t key = dec_key(emask, out_node);
+// The compiled form of the pattern of `key` (dec_key), built once per handle (caller holds c->mu).
+const te_clay::DecCache *dec_pattern(te_clay *c, uint64_t key) {
     auto f = c->dec_cache.find(key);
     if (f != c->dec_cache.end()) return &f->second;
     te_clay::DecCache d;
-    if (!compile_pattern(c->h, emask, out_node, d)) return nullptr;
+    if (!compile_pattern(c->h, dec_key_emask(key), dec_key_out_node(key), d)) return nullptr;
     return &c->dec_cache.emplace(key, std::move(d)).first->second;
 }
 
 // Compile the patterns of `keys` missing from the cache, on up to 16 host threads (random
 // survivor sets bring one new pattern per stripe: ~150 us of host work each).
-void dec_precompile(te_clay *c, const std::vector<std::pair<uint64_t, int>> &keys) {
-    std::vector<std::pair<uint64_t, int>> todo;
-    for (const auto &k : keys)
-        if (!c->dec_cache.count(dec_key(k.first, k.second))) todo.push_back(k);
+void dec_precompile(te_clay *c, const std::vector<uint64_t> &keys) {
+    std::vector<uint64_t> todo;
+    for (uint64_t k : keys)
+        if (!c->dec_cache.count(k)) todo.push_back(k);
     if (todo.size() < 8) return;  // dec_pattern compiles the few inline
     std::vector<te_clay::DecCache> out(todo.size());
     std::vector<char> ok(todo.size(), 0);
@@ -1355,14 +1280,14 @@ void dec_precompile(te_clay *c, const std::vector<std::pair<uint64_t, int>> &key
     std::atomic<size_t> next{0};
     auto work = [&] {
         for (size_t i; (i = next.fetch_add(1)) < todo.size();)
-            ok[i] = compile_pattern(c->h, todo[i].first, todo[i].second, out[i]);
+            ok[i] = compile_pattern(c->h, dec_key_emask(todo[i]), dec_key_out_node(todo[i]), out[i]);
     };
     std::vector<std::thread> th;
     for (size_t t = 1; t < nth; t++) th.emplace_back(work);
     work();
     for (auto &t : th) t.join();
     for (size_t i = 0; i < todo.size(); i++)
-        if (ok[i]) c->dec_cache.emplace(dec_key(todo[i].first, todo[i].second), std::move(out[i]));
+        if (ok[i]) c->dec_cache.emplace(todo[i], std::move(out[i]));
 }
 
 // Slots of the device-resident pattern store (te_clay::DecStore) for the staged patterns of one
@@ -1438,395 +1363,253 @@ bool dec_store_slots(te_clay *c, const std::vector<const te_clay::DecCache *> &c
     return true;
 }
 
-// A decode call of at most this many stripes is a per-call decode: one wave per workgroup.
-constexpr size_t kDecSmallStripes = 64;
+// One arena's gather launch (if any job), then its metadata launch (if any)
+int gather_meta_enqueue(Arena &A, hipStream_t s, const std::vector<CopyJob> &copies, const std::vector<MetaJob> &metas) {
+    A.img.clear();
+    const size_t off = A.put(copies.data(), copies.size() * sizeof(CopyJob));
+    const size_t moff = A.put(metas.data(), metas.size() * sizeof(MetaJob));
+    const int r = A.upload(s);
+    if (r) return r;
+    KTimer kt(s);
+    if (!copies.empty()) TE_HIP(launch_gather(A.at<CopyJob>(off), (uint32_t)copies.size(), s));
+    if (!metas.empty()) TE_HIP(launch_meta(A.at<MetaJob>(moff), (uint32_t)metas.size(), 1u, s));
+    kt.stop();
+    return A.mark_done(s);
+}
+// A pattern with a per-pattern kernel built (dec_rtc.cpp): its jobs leave their group for a launch of their own
+struct DecFixed { DecGroupKey key; const DecJitKernel *k; std::vector<GpeJob> jobs; size_t off = 0; };
 
-// Items with lost >= 0 (node recover) need the staged kernel: TE_ERR_UNSUPPORTED, before anything
-// is enqueued, when a pattern has no plane program (the caller then decodes and re-encodes).
-int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const DecItem *items,
-                   size_t nitems, uint8_t *d_out, hipStream_t s, bool raw) {
-    const ClayHost &h = c->h;
-    const int n = h.n;
-    const int rotated = (cfg && !raw) ? cfg->rotated : 0;
-    static_assert(TE_DECODE_CLASSES == kDecClasses, "te_decode_launch_stats counts every class");
-    te_decode_launch_stats &dls = c->dls;  // summed: the calling entry point zeroed it
-    // compiled programs kept on the host: <= ~430 MB (26 KB per pattern, as many as the device
-    // store's cap; 77,520 masks exist for k = 7, x 20 outputs for node recover)
-    if (c->dec_cache.size() > std::max<size_t>(c->dstore.max_cap, nitems)) c->dec_cache.clear();
-    std::vector<std::vector<RangeWin>> wins(nitems);  // ranged items: their touched stripes' windows
-    {
-        std::vector<std::pair<uint64_t, int>> keys;
-        std::unordered_map<uint64_t, char> seen;
-        for (size_t i = 0; i < nitems; i++) {
-            const DecItem &it = items[i];
-            uint64_t sb = 0, se = it.ns;
-            if (it.ranged) {
-                range_stripes(it.stripe, it.w_start, it.w_len, sb, se);
-                wins[i] = range_windows(n, rotated, it.avail, it.blob_len, it.stripe, it.cs, it.w_start, it.w_len);
-            }
-            for (uint64_t st = sb; st < se; st++) {
-                if (it.ranged && wins[i][st - sb].copy) continue;
-                const uint64_t emask = stripe_emask(h, rotated, it.avail, st);
-                const int onode = it.lost >= 0 ? h.ext_to_int((int)te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st,
-                                                                                      (uint32_t)it.lost))
-                                  : it.ranged && range_is_chunk(it, wins[i][st - sb]) ? h.ext_to_int((int)wins[i][st - sb].miss_x) : -1;
-                if (seen.emplace(dec_key(emask, onode), 1).second) keys.push_back({emask, onode});
-            }
-        }
-        dec_precompile(c, keys);
+// What the steps of one decode_enqueue call share
+struct DecCall {
+    te_clay *c; hipStream_t s; int rotated;
+    DecPlan plan;
+    std::vector<const te_clay::DecCache *> cached;  // by pattern id (plan.keys)
+    bool staged = true;  // every pattern compiles to a plane program (decode_stage.hip, the class kernels)
+    uint32_t lds_rows = 0, nscr_max = 0, max_er = 0;
+    std::vector<DecFixed> fixed;
+    DecRoute route;
+    // staged patterns live in the device store (uploaded once per handle), the jobs name slots;
+    // otherwise (generic kernel, or more patterns than the store holds) they go in the arena
+    bool in_store = false;
+    StoreFill fill;
+    std::vector<std::pair<DecGroupKey, size_t>> offs;  // the table groups left non-empty: their jobs in the arena
+    size_t pat_off = 0, pool_off = 0, hdr_off = 0, step_off = 0, soff_off = 0, copy_off = 0;
+    size_t fp_off = 0, fh_off = 0, fs_off = 0, fo_off = 0;  // new store entries
+    bool small_dec = false;  // one wave per workgroup
+    uint32_t class_g = 2;
+    int class_streams = 1;  // streams the class groups run on, side by side
+    uint8_t *scratch = nullptr, *cls_scratch = nullptr;
+
+    bool staged_group(const DecGroupKey &k) const { return staged && dec_geom_staged(c->h, k.cs, k.slice_len); }
+    uint32_t sc(const DecGroupKey &k) const { return (uint32_t)(k.cs / (uint64_t)c->h.alpha); }
+    const GpePattern *pats() const { return in_store ? c->dstore.pats.as<GpePattern>() : c->dec.at<GpePattern>(pat_off); }
+};
+// Step 2: every key's compiled pattern
+int dec_resolve(DecCall &D) {
+    dec_precompile(D.c, D.plan.keys);
+    for (uint64_t key : D.plan.keys) {
+        const te_clay::DecCache *dc = dec_pattern(D.c, key);
+        if (!dc) return TE_ERR_BAD_ENCODING;
+        D.cached.push_back(dc);
+        D.max_er = std::max(D.max_er, dc->P.nerased);
     }
-    std::unordered_map<uint64_t, uint32_t> pat_index;  // erased mask (| output node << 48) -> pattern id
-    std::vector<uint64_t> pat_keys;                    // by pattern id
-    bool fused = false;
-    std::vector<GpePattern> pats;  // the generic kernel's per-call copies (built only for it)
-    std::vector<const te_clay::DecCache *> cached;
-    std::vector<uint16_t> pool;
-    std::map<uint64_t, std::vector<GpeJob>> groups;  // by chunk size
-    std::map<uint64_t, uint64_t> group_in_stride;
-    uint32_t max_er = 0;
-    // ranged reads: a copy stripe's window is gathered from the present data chunks (one launch
-    // for the call), a decode stripe's job carries its window [out_lo, out_len)
-    // a chunk stripe (TE_RANGE_CHUNK): the present chunks' pieces join the gather, the one erased
-    // chunk's piece is a windowed recover job of its own groups (by chunk size, as `groups`)
-    std::vector<CopyJob> copies;
-    std::map<uint64_t, std::vector<GpeJob>> chunk_groups;
-    bool ranged_call = false;
-    for (size_t i = 0; i < nitems; i++) {
-        const DecItem &it = items[i];
-        uint64_t sb = 0, se = it.ns;
-        if (it.ranged) range_stripes(it.stripe, it.w_start, it.w_len, sb, se);
-        ranged_call = ranged_call || it.ranged;
-        for (uint64_t st = sb; st < se; st++) {
-            RangeWin win{0, 0, false};
-            bool chunk = false;  // rebuild chunk win.miss_x alone
-            if (it.ranged) {
-                win = wins[i][st - sb];
-                chunk = range_is_chunk(it, win);
-                c->rgs.stripes_touched++;
-                if (win.copy || chunk) {
-                    if (chunk) c->rcs.stripes_rebuilt++;
-                    else c->rgs.stripes_copied++;
-                    for (uint64_t x = win.lo / it.cs; x * it.cs < win.hi; x++) {
-                        if (chunk && x == win.miss_x) continue;
-                        const uint64_t a = std::max(win.lo, x * it.cs), b = std::min(win.hi, (x + 1) * it.cs);
-                        const uint32_t sl = te_shard_to_slice(rotated, (uint32_t)n, (uint32_t)st, (uint32_t)x);
-                        CopyJob cj{};
-                        cj.src = d_slices + it.in_base + sl * it.slice_len + (st * it.cs - it.in_skew) + (a - x * it.cs);
-                        cj.dst = d_out + it.out_off + (st * it.stripe + a - it.w_start);
-                        cj.len = cj.valid = b - a;
-                        copies.push_back(cj);
-                        c->rcs.gather_jobs += chunk;
-                    }
-                    if (!chunk) continue;
-                } else {
-                    c->rgs.stripes_decoded++;
-                }
-            }
-            const uint64_t emask = stripe_emask(h, rotated, it.avail, st);
-            // the output node: recover's lost slice's shard, a chunk stripe's erased data shard
-            const int onode = it.lost >= 0 ? h.ext_to_int((int)te_slice_to_shard(rotated, (uint32_t)n, (uint32_t)st,
-                                                                                  (uint32_t)it.lost))
-                              : chunk ? h.ext_to_int((int)win.miss_x) : -1;
-            fused = fused || it.lost >= 0;
-            const uint64_t pkey = emask | (uint64_t)(onode + 1) << 48;
-            auto f = pat_index.find(pkey);
-            uint32_t pid;
-            if (f == pat_index.end()) {
-                const te_clay::DecCache *dc = dec_pattern(c, emask, onode);
-                if (!dc) return TE_ERR_BAD_ENCODING;
-                pid = (uint32_t)cached.size();
-                cached.push_back(dc);
-                pat_index[pkey] = pid;
-                pat_keys.push_back(pkey);
-                max_er = std::max(max_er, dc->P.nerased);
-            } else {
-                pid = f->second;
-            }
-            GpeJob g{};
-            g.in = d_slices + it.in_base + (st * it.cs - it.in_skew);
-            g.in_len = ~0ull;
-            if (chunk) {
-                // `out` is the address of the erased chunk's byte 0 (below the caller's range when
-                // the window starts inside the chunk), the window [out_lo, out_len) in chunk bytes
-                const uint64_t x0 = win.miss_x * it.cs;
-                g.out = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(d_out) + it.out_off + st * it.stripe + x0 - it.w_start);
-                g.out_lo = std::max(win.lo, x0) - x0;
-                g.out_len = std::min(win.hi, x0 + it.cs) - x0;
-                c->rcs.bytes_stored += g.out_len - g.out_lo;
-            } else if (onode >= 0) {  // the lost slice's chunk of this stripe, whole
-                g.out = d_out + it.out_off + st * it.cs;
-                g.out_len = it.cs;
-            } else if (it.ranged) {
-                // `out` stays the address of stripe byte 0: for a window's first stripe that is
-                // below the caller's range by out_lo bytes, which the kernels never store to
-                g.out = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(d_out) + it.out_off + st * it.stripe - it.w_start);
-                g.out_lo = win.lo;
-                g.out_len = win.hi;
-            } else {
-                g.out = d_out + it.out_off + st * (raw ? 0 : it.stripe);
-                g.out_len = raw ? it.cs * (uint64_t)h.k : (st + 1 == it.ns ? it.blob_len - st * it.stripe : it.stripe);
-            }
-            g.rot = rotated ? (uint32_t)((st * TE_ROTATION_STEP) % n) : 0u;
-            g.pattern = pid;
-            auto key = (it.cs << 32) ^ it.slice_len;
-            (chunk ? chunk_groups : groups)[key].push_back(g);
-            group_in_stride[key] = it.slice_len;
-        }
+    for (const te_clay::DecCache *dc : D.cached) {
+        if (!(D.staged = dc->staged)) break;
+        D.lds_rows = std::max(D.lds_rows, decode_stage_rows(dc->H.nslots, dc->H.max_out));
+        D.nscr_max = std::max(D.nscr_max, dc->H.nscratch);
     }
-    c->rgs.gather_jobs += copies.size();
-    if (groups.empty() && chunk_groups.empty()) {  // nothing to decode: a ranged call of copy stripes only (or of nothing)
-        if (copies.empty()) return TE_OK;
-        Arena &A = c->dec;
-        A.img.clear();
-        const size_t off = A.put(copies.data(), copies.size() * sizeof(CopyJob));
-        int r = A.upload(s);
-        if (r) return r;
-        KTimer kt(s);
-        TE_HIP(launch_gather(A.at<CopyJob>(off), (uint32_t)copies.size(), s));
-        kt.stop();
-        return A.mark_done(s);
-    }
-    // staged kernel (decode_stage.hip) when every pattern compiles to a plane program; of the two
-    // row orientations the one with fewer scratch rows
-    uint32_t lds_rows = 0, nscr_max = 0;
-    bool staged = true;
-    for (size_t i = 0; i < cached.size() && staged; i++) {
-        const te_clay::DecCache &dc = *cached[i];
-        staged = dc.staged;
-        if (!staged) break;
-        lds_rows = std::max(lds_rows, decode_stage_rows(dc.H.nslots, dc.H.max_out));
-        nscr_max = std::max(nscr_max, dc.H.nscratch);
-    }
-    lds_rows = std::max(lds_rows, 1u);
-    // the staged kernel addresses a stripe's slices and its output share with 31-bit offsets
-    auto staged_group = [&](uint64_t key) {
-        const uint64_t cs = key >> 32, sc = cs / (uint64_t)h.alpha;
-        return staged && sc >= 8 && (uint64_t)n * group_in_stride[key] < 0x7fffffffull &&
-               cs * (uint64_t)h.k < 0x7fffffffull;
-    };
-    if (fused)
-        for (auto &kv : groups)
-            if (!staged_group(kv.first)) return TE_ERR_UNSUPPORTED;
-    // patterns with a per-pattern kernel built (dec_rtc.cpp) leave their group for a launch of
-    // their own; every staged stripe counts toward building its pattern's kernel
-    struct Fixed { uint64_t key; const DecJitKernel *k; std::vector<GpeJob> jobs; size_t off = 0; };
+    D.lds_rows = std::max(D.lds_rows, 1u);
+    return TE_OK;
+}
+// Step 3: patterns with a per-pattern kernel built (dec_rtc.cpp) leave their group for a launch of
+// their own; every staged stripe counts toward building its pattern's kernel.
+// (pattern kernels write data chunks whole: recover's outputs are other nodes, and a ranged
+// call's jobs carry a window the pattern kernels do not clip)
+void dec_pick_jit(DecCall &D) {
+    te_clay *c = D.c;
+    if (!D.staged || D.plan.fused || D.plan.ranged_call) return;
     constexpr uint64_t kJitMinStripes = 512;  // two workgroups per CU
     // a caller that lowered the build threshold (te_clay_set_decode_jit, tests) lowers the floor too
     const uint64_t jit_floor = c->jit_mode >= 0 ? std::min<uint64_t>(kJitMinStripes, c->jit_min) : kJitMinStripes;
-    std::vector<Fixed> fixed;
-    static const bool class_on = [] {
-        const char *e = tec_knob("TEC_DEC_CLASS");
-        return !(e && e[0] == '0');
-    }();
-    // (pattern kernels write data chunks whole: recover's outputs are other nodes, and a ranged
-    // call's jobs carry a window the pattern kernels do not clip)
-    if (staged && !fused && !ranged_call) {
-        if (!c->jit) {
-            c->jit = dec_jit_new(c->device);
-            if (c->jit_mode >= 0) dec_jit_set(c->jit, c->jit_mode, c->jit_min);
-        }
-        for (auto &kv : groups) {
-            if (!staged_group(kv.first)) continue;
-            const uint32_t sc = (uint32_t)((kv.first >> 32) / (uint64_t)h.alpha);
-            const DecJitGeom geo = dec_jit_geom(sc);
-            std::vector<uint64_t> cnt(cached.size(), 0);
-            for (const GpeJob &g : kv.second) cnt[g.pattern]++;
-            std::vector<int> fx(cached.size(), -1);
-            for (size_t p = 0; p < cached.size(); p++) {
-                // a pattern kernel gets a launch of its own: only worth it for a group that fills
-                // the GPU; smaller groups stay in the shared table-driven launch (recover's
-                // windows hold ~64 stripes per pattern: 80 small launches per step ran 29.3 ms
-                // against 14.5 for the shared one).  Such groups do not count toward building a
-                // kernel either: it could never be launched for them.
-                if (cnt[p] < std::max<uint64_t>(1, jit_floor)) continue;
-                // a survivor set with a class kernel runs it: after the load fusions the class
-                // kernels time at or below the hipRTC pattern kernels (4.26 vs 4.36-4.39 ms, worst
-                // case, same box) with no 25 s compile; a caller that asked for the pattern kernels
-                // (te_clay_set_decode_jit) still gets them
-                if (c->jit_mode < 0 && class_on && dec_class_of(h, cached[p]->P) >= 0) continue;
-                const DecJitKernel *k = dec_jit_get(c->jit, h, cached[p]->P, cached[p]->orient, (int)geo.G, (int)geo.wb, cnt[p]);
-                if (!k) continue;
-                fx[p] = (int)fixed.size();
-                fixed.push_back(Fixed{kv.first, k, {}});
-            }
-            std::vector<GpeJob> rest;
-            for (const GpeJob &g : kv.second) {
-                if (fx[g.pattern] >= 0) fixed[fx[g.pattern]].jobs.push_back(g);
-                else rest.push_back(g);
-            }
-            kv.second.swap(rest);
-        }
+    if (!c->jit) {
+        c->jit = dec_jit_new(c->device);
+        if (c->jit_mode >= 0) dec_jit_set(c->jit, c->jit_mode, c->jit_min);
     }
-    // decode class kernels (decode_class.hip, dec_class.hpp): the remaining stripes of every
-    // Clay(20,7,16) survivor set run the ahead-of-time kernel of the set's class -- the program's
-    // control compiled in, the set's slices, planes and decoding matrix read at run time.
-    // Measurement option TEC_DEBUG_KNOBS=1 TEC_DEC_CLASS=0: the table-driven kernel instead.
-    struct ClassGrp { uint64_t key; int id; std::vector<GpeJob> jobs; size_t off = 0; };
-    std::vector<ClassGrp> cls;
-    bool cls_small = false;  // the class stripes fit one round of per-call workgroups
-    // measurement option TEC_DEC_CLASS_SMALL=1 (off by default: per call 64 MiB, kernel 0.596 ms
-    // on the per-call class kernels against 0.472 on the one table-driven launch)
-    static const bool small_dec_cls = [] {
-        const char *e = tec_knob("TEC_DEC_CLASS_SMALL");
-        return e && e[0] == '1';
-    }();
-    // streams the class groups of a call run on, side by side (TEC_DEC_CLASS_STREAMS)
+    const size_t np = D.cached.size();
+    for (auto &kv : D.plan.groups) {
+        if (!D.staged_group(kv.first)) continue;
+        const DecJitGeom geo = dec_jit_geom(D.sc(kv.first));
+        std::vector<uint64_t> cnt(np, 0);
+        for (const GpeJob &g : kv.second) cnt[g.pattern]++;
+        std::vector<int> fx(np, -1);
+        for (size_t p = 0; p < np; p++) {
+            // a pattern kernel gets a launch of its own: only worth it for a group that fills
+            // the GPU; smaller groups stay in the shared table-driven launch (recover's
+            // windows hold ~64 stripes per pattern: 80 small launches per step ran 29.3 ms
+            // against 14.5 for the shared one).  Such groups do not count toward building a
+            // kernel either: it could never be launched for them.
+            if (cnt[p] < std::max<uint64_t>(1, jit_floor)) continue;
+            // a survivor set with a class kernel runs it: after the load fusions the class
+            // kernels time at or below the hipRTC pattern kernels (4.26 vs 4.36-4.39 ms, worst
+            // case, same box) with no 25 s compile; a caller that asked for the pattern kernels
+            // (te_clay_set_decode_jit) still gets them
+            if (c->jit_mode < 0 && dec_class_on() && dec_class_of(c->h, D.cached[p]->P) >= 0) continue;
+            const DecJitKernel *k = dec_jit_get(c->jit, c->h, D.cached[p]->P, D.cached[p]->orient, (int)geo.G, (int)geo.wb, cnt[p]);
+            if (!k) continue;
+            fx[p] = (int)D.fixed.size();
+            D.fixed.push_back(DecFixed{kv.first, k, {}});
+        }
+        std::vector<GpeJob> rest;
+        for (const GpeJob &g : kv.second) {
+            if (fx[g.pattern] >= 0) D.fixed[fx[g.pattern]].jobs.push_back(g);
+            else rest.push_back(g);
+        }
+        kv.second.swap(rest);
+    }
+}
+// Step 4: the class kernels' share (dec_route, dec_plan.hpp), with this process's knobs
+int dec_route_call(DecCall &D) {
+    // measurement option TEC_DEC_CLASS_SMALL=1 (off by default)
+    static const bool small_dec_cls = [] { const char *e = tec_knob("TEC_DEC_CLASS_SMALL"); return e && e[0] == '1'; }();
     static const int class_streams = [] {
         const char *e = tec_knob("TEC_DEC_CLASS_STREAMS");
         const int v = e ? atoi(e) : 4;  // the process's hardware queues (GPU_MAX_HW_QUEUES default)
         return std::max(1, std::min(v, 1 + te_clay::kClsSide));
     }();
-    if (staged && class_on) {
-        std::vector<int> cid(cached.size(), -1);
-        for (size_t p = 0; p < cached.size(); p++) {
-            const int onode = (int)(pat_keys[p] >> 48) - 1;  // >= 0: node recover's output node
-            const int id = dec_class_of(h, cached[p]->P, onode);
-            cid[p] = id >= 0 && dec_class_info(id, nullptr, nullptr) ? id : -1;
-        }
-        for (auto &kv : groups) {
-            if (!staged_group(kv.first)) continue;
-            int at[kDecClasses];
-            std::fill(at, at + kDecClasses, -1);
-            std::vector<GpeJob> rest;
-            for (const GpeJob &g : kv.second) {
-                const int id = cid[g.pattern];
-                if (id < 0) {
-                    rest.push_back(g);
-                    continue;
-                }
-                if (at[id] < 0) {
-                    at[id] = (int)cls.size();
-                    cls.push_back(ClassGrp{kv.first, id, {}});
-                }
-                cls[(size_t)at[id]].jobs.push_back(g);
-            }
-            kv.second.swap(rest);
-        }
-        // a call that does not fill the GPU is bound by one stripe's 100-step chain per launch:
-        // with more class groups than streams some launches would run after others, so such a
-        // call runs on the table-driven kernel in one launch (per call 64 MiB: 3.67 ms as
-        // classes against 3.00, r06)
-        // (per-call decodes of <= 64 stripes run the classes' one-wave kernels, whose input loads
-        // lead by four steps: their chains are short enough to run a few one after another)
-        // (TEC_DEC_CLASS_SMALL=1: a call whose class stripes fit one round of per-call workgroups
-        // -- G = 1, 4 compute waves and a loader wave per 64-column group, <= 2 per CU by LDS --
-        // runs them on the per-call kernels instead; measured slower for 64 MiB per call)
-        size_t ncls = 0, nall = 0, small_wgs = 0;
-        for (const ClassGrp &cg : cls) {
-            ncls += cg.jobs.size();
-            const uint64_t sc = (cg.key >> 32) / (uint64_t)h.alpha;
-            small_wgs += cg.jobs.size() * (size_t)((sc / 4 + 63) / 64);
-        }
-        for (auto &kv : groups) nall += kv.second.size();
-        cls_small = small_dec_cls && !cls.empty() && small_wgs <= 512;
-        if (!cls_small && cls.size() > (size_t)class_streams && ncls < 1024 && ncls + nall > kDecSmallStripes) {
-            for (ClassGrp &cg : cls) groups[cg.key].insert(groups[cg.key].end(), cg.jobs.begin(), cg.jobs.end());
-            cls.clear();
-        }
-    }
-    // chunk stripes (TE_RANGE_CHUNK): each on the windowed kernel of its recover class, a launch
-    // per class beside the decode classes' (they never join the table-driven launch above: only
-    // the class kernels clip a recover job's window).  range_chunk_ok admitted the object, so a
-    // missing kernel here is an error, not a reason to decode the stripe another way.
-    for (auto &kv : chunk_groups) {
-        if (!staged || !class_on || !staged_group(kv.first)) return TE_ERR_UNSUPPORTED;
-        int at[kDecClassKernels];
-        std::fill(at, at + kDecClassKernels, -1);
-        for (const GpeJob &g : kv.second) {
-            const int onode = (int)(pat_keys[g.pattern] >> 48) - 1;
-            const int id = dec_class_win_id(dec_class_of(h, cached[g.pattern]->P, onode));
-            if (id < 0 || !dec_class_info(id, nullptr, nullptr)) return TE_ERR_UNSUPPORTED;
-            if (at[id] < 0) {
-                at[id] = (int)cls.size();
-                cls.push_back(ClassGrp{kv.first, id, {}});
-            }
-            cls[(size_t)at[id]].jobs.push_back(g);
-        }
-    }
-    // staged patterns live in the device store (uploaded once per handle), the jobs name slots;
-    // otherwise (generic kernel, or more patterns than the store holds) they go in the arena
+    D.class_streams = class_streams;
+    std::vector<int> pat_class(D.cached.size());
+    for (size_t p = 0; p < D.cached.size(); p++)  // (an output node >= 0: node recover's, a chunk stripe's)
+        pat_class[p] = dec_class_of(D.c->h, D.cached[p]->P, dec_key_out_node(D.plan.keys[p]));
+    D.route = dec_route(D.c->h, D.staged, pat_class, [](int id) { return dec_class_info(id, nullptr, nullptr); },
+                        D.plan.groups, D.plan.chunk_groups, dec_class_on(), class_streams, small_dec_cls);
+    return D.route.err;
+}
+// Step 5: the patterns' store slots, and the call's descriptors in the arena's host image
+int dec_image(DecCall &D) {
+    te_clay *c = D.c;
+    DecGroups &groups = D.plan.groups;
     std::vector<uint32_t> slot_of;
-    StoreFill fill;
-    bool in_store = false;
-    bool every_group_staged = staged;  // the generic kernel reads per-call patterns (plane lists)
-    for (auto &kv : groups) every_group_staged = every_group_staged && (kv.second.empty() || staged_group(kv.first));
+    bool every_group_staged = D.staged;  // the generic kernel reads per-call patterns (plane lists)
+    for (auto &kv : groups) every_group_staged = every_group_staged && (kv.second.empty() || D.staged_group(kv.first));
     if (every_group_staged) {
         int rs = TE_OK;
-        in_store = dec_store_slots(c, cached, pat_keys, slot_of, fill, rs);
+        D.in_store = dec_store_slots(c, D.cached, D.plan.keys, slot_of, D.fill, rs);
         if (rs) return rs;
-        if (in_store) {
+        if (D.in_store) {
             for (auto &kv : groups)
                 for (GpeJob &g : kv.second) g.pattern = slot_of[g.pattern];
-            for (ClassGrp &cg : cls)
+            for (DecClassGrp &cg : D.route.cls)
                 for (GpeJob &g : cg.jobs) g.pattern = slot_of[g.pattern];
         }
     }
-    std::vector<DecProgHdr> dhdrs;
-    std::vector<DecStepP> dsteps;
-    std::vector<uint32_t> dstep_off;
-    if (staged && !in_store) {
-        for (size_t i = 0; i < cached.size(); i++) {
-            dhdrs.push_back(cached[i]->H);
-            dstep_off.push_back((uint32_t)dsteps.size());
-            dsteps.insert(dsteps.end(), cached[i]->steps.begin(), cached[i]->steps.end());
-        }
-    }
-    if (!in_store)
-        for (const te_clay::DecCache *dc : cached) {
+    std::vector<GpePattern> pats;  // the per-call copies (not in the store): patterns and plane lists, programs
+    std::vector<uint16_t> pool;
+    std::vector<DecProgHdr> dhdrs; std::vector<DecStepP> dsteps; std::vector<uint32_t> dstep_off;
+    const bool progs = D.staged && !D.in_store;
+    if (!D.in_store)
+        for (const te_clay::DecCache *dc : D.cached) {
+            if (progs) {
+                dhdrs.push_back(dc->H);
+                dstep_off.push_back((uint32_t)dsteps.size());
+                dsteps.insert(dsteps.end(), dc->steps.begin(), dc->steps.end());
+            }
             pats.push_back(dc->P);
             pats.back().planes_off = (uint32_t)pool.size();
             pool.insert(pool.end(), dc->planes.begin(), dc->planes.end());
         }
     Arena &A = c->dec;
     A.img.clear();
-    const size_t pat_off = in_store ? 0 : A.put(pats.data(), pats.size() * sizeof(GpePattern));
-    const size_t pool_off = A.put(pool.data(), pool.size() * sizeof(uint16_t));
-    size_t hdr_off = 0, step_off = 0, soff_off = 0;
-    if (staged && !in_store) {
-        hdr_off = A.put(dhdrs.data(), dhdrs.size() * sizeof(DecProgHdr));
-        step_off = A.put(dsteps.data(), dsteps.size() * sizeof(DecStepP), 64);
-        soff_off = A.put(dstep_off.data(), dstep_off.size() * sizeof(uint32_t));
+    D.pat_off = D.in_store ? 0 : A.put(pats.data(), pats.size() * sizeof(GpePattern));
+    D.pool_off = A.put(pool.data(), pool.size() * sizeof(uint16_t));
+    if (progs) {
+        D.hdr_off = A.put(dhdrs.data(), dhdrs.size() * sizeof(DecProgHdr));
+        D.step_off = A.put(dsteps.data(), dsteps.size() * sizeof(DecStepP), 64);
+        D.soff_off = A.put(dstep_off.data(), dstep_off.size() * sizeof(uint32_t));
     }
-    std::vector<std::pair<uint64_t, size_t>> offs;
     for (auto &kv : groups)
-        if (!kv.second.empty()) offs.push_back({kv.first, A.put(kv.second.data(), kv.second.size() * sizeof(GpeJob))});
-    for (Fixed &f : fixed) f.off = A.put(f.jobs.data(), f.jobs.size() * sizeof(GpeJob));
-    for (ClassGrp &cg : cls) cg.off = A.put(cg.jobs.data(), cg.jobs.size() * sizeof(GpeJob));
-    const size_t copy_off = A.put(copies.data(), copies.size() * sizeof(CopyJob));
+        if (!kv.second.empty()) D.offs.push_back({kv.first, A.put(kv.second.data(), kv.second.size() * sizeof(GpeJob))});
+    for (DecFixed &f : D.fixed) f.off = A.put(f.jobs.data(), f.jobs.size() * sizeof(GpeJob));
+    for (DecClassGrp &cg : D.route.cls) cg.off = A.put(cg.jobs.data(), cg.jobs.size() * sizeof(GpeJob));
+    D.copy_off = A.put(D.plan.copies.data(), D.plan.copies.size() * sizeof(CopyJob));
     // new store entries ride in the same upload, then move to their slots on this stream
-    size_t fp_off = 0, fh_off = 0, fs_off = 0, fo_off = 0;
-    if (in_store && !fill.pats.empty()) {
-        fp_off = A.put(fill.pats.data(), fill.pats.size() * sizeof(GpePattern));
-        fh_off = A.put(fill.hdrs.data(), fill.hdrs.size() * sizeof(DecProgHdr));
-        fs_off = A.put(fill.steps.data(), fill.steps.size() * sizeof(DecStepP), 64);
+    const StoreFill &fill = D.fill;
+    if (D.in_store && !fill.pats.empty()) {
+        D.fp_off = A.put(fill.pats.data(), fill.pats.size() * sizeof(GpePattern));
+        D.fh_off = A.put(fill.hdrs.data(), fill.hdrs.size() * sizeof(DecProgHdr));
+        D.fs_off = A.put(fill.steps.data(), fill.steps.size() * sizeof(DecStepP), 64);
     }
-    if (in_store && !fill.soff.empty()) fo_off = A.put(fill.soff.data(), fill.soff.size() * sizeof(uint32_t));
+    if (D.in_store && !fill.soff.empty()) D.fo_off = A.put(fill.soff.data(), fill.soff.size() * sizeof(uint32_t));
+    return TE_OK;
+}
+// Step 6: the descriptors go up; new store entries move to their slots on the call's stream
+int dec_upload(DecCall &D) {
+    Arena &A = D.c->dec;
+    hipStream_t s = D.s;
     int r = A.upload(s);
-    if (r) return r;
-    if (in_store) {
-        te_clay::DecStore &S = c->dstore;
-        if (fill.wait_used) TE_HIP(S.readers.wait(s));
-        // entries another stream filled and nobody on this stream has waited for yet
-        if (S.written_pending && S.written_stream != s) TE_HIP(hipStreamWaitEvent(s, S.written, 0));
-        const bool any = !fill.pats.empty() || !fill.soff.empty();
-        if (!fill.pats.empty()) {
-            const size_t np = fill.pats.size();
-            TE_HIP(hipMemcpyAsync(S.pats.as<GpePattern>() + fill.n0, A.at<GpePattern>(fp_off), np * sizeof(GpePattern),
-                                  hipMemcpyDeviceToDevice, s));
-            TE_HIP(hipMemcpyAsync(S.hdrs.as<DecProgHdr>() + fill.n0, A.at<DecProgHdr>(fh_off), np * sizeof(DecProgHdr),
-                                  hipMemcpyDeviceToDevice, s));
-            TE_HIP(hipMemcpyAsync(S.steps.as<DecStepP>() + (size_t)fill.n0 * te_clay::DecStore::kSteps,
-                                  A.at<DecStepP>(fs_off), fill.steps.size() * sizeof(DecStepP), hipMemcpyDeviceToDevice, s));
-        }
-        if (!fill.soff.empty())
-            TE_HIP(hipMemcpyAsync(S.soff.p, A.at<uint32_t>(fo_off), fill.soff.size() * sizeof(uint32_t),
-                                  hipMemcpyDeviceToDevice, s));
-        if (any) {
-            TE_HIP(hipEventRecord(S.written, s));
-            S.written_pending = true;
-            S.written_stream = s;
-        }
+    if (r || !D.in_store) return r;
+    te_clay::DecStore &S = D.c->dstore;
+    const StoreFill &fill = D.fill;
+    if (fill.wait_used) TE_HIP(S.readers.wait(s));
+    // entries another stream filled and nobody on this stream has waited for yet
+    if (S.written_pending && S.written_stream != s) TE_HIP(hipStreamWaitEvent(s, S.written, 0));
+    if (!fill.pats.empty()) {
+        const size_t np = fill.pats.size();
+        TE_HIP(hipMemcpyAsync(S.pats.as<GpePattern>() + fill.n0, A.at<GpePattern>(D.fp_off), np * sizeof(GpePattern),
+                              hipMemcpyDeviceToDevice, s));
+        TE_HIP(hipMemcpyAsync(S.hdrs.as<DecProgHdr>() + fill.n0, A.at<DecProgHdr>(D.fh_off), np * sizeof(DecProgHdr),
+                              hipMemcpyDeviceToDevice, s));
+        TE_HIP(hipMemcpyAsync(S.steps.as<DecStepP>() + (size_t)fill.n0 * te_clay::DecStore::kSteps,
+                              A.at<DecStepP>(D.fs_off), fill.steps.size() * sizeof(DecStepP), hipMemcpyDeviceToDevice, s));
     }
+    if (!fill.soff.empty())
+        TE_HIP(hipMemcpyAsync(S.soff.p, A.at<uint32_t>(D.fo_off), fill.soff.size() * sizeof(uint32_t),
+                              hipMemcpyDeviceToDevice, s));
+    if (!fill.pats.empty() || !fill.soff.empty()) {
+        TE_HIP(hipEventRecord(S.written, s));
+        S.written_pending = true;
+        S.written_stream = s;
+    }
+    return TE_OK;
+}
+DecArgs dec_table_args(const DecCall &D, const std::pair<DecGroupKey, size_t> &o) {
+    const te_clay *c = D.c;
+    const Arena &A = c->dec;
+    const te_clay::DecStore &S = c->dstore;
+    DecArgs a{};
+    a.jobs = A.at<GpeJob>(o.second);
+    a.patterns = D.pats();
+    a.hdrs = D.in_store ? S.hdrs.as<DecProgHdr>() : A.at<DecProgHdr>(D.hdr_off);
+    a.steps = D.in_store ? S.steps.as<DecStepP>() : A.at<DecStepP>(D.step_off);
+    a.step_off = D.in_store ? S.soff.as<uint32_t>() : A.at<uint32_t>(D.soff_off);
+    a.njobs = (uint32_t)D.plan.groups.at(o.first).size();
+    a.sc = D.sc(o.first);
+    a.words_per_stripe = (a.sc + 3) / 4;
+    a.cs = (uint32_t)o.first.cs; a.n = (uint32_t)c->h.n; a.nk = (uint32_t)c->h.k;
+    a.lds_rows = D.lds_rows;
+    a.nscratch_max = D.nscr_max;
+    a.in_stride = o.first.slice_len;
+    a.out_stride = o.first.cs;
+    a.gmax = D.small_dec ? 1u : 0u;
+    return a;
+}
+dfix_args dec_fixed_args(const DecCall &D, const DecFixed &f) {
+    dfix_args a{};
+    a.jobs = reinterpret_cast<const dfix::Job *>(D.c->dec.at<GpeJob>(f.off));
+    a.scratch = D.scratch;
+    a.in_stride = f.key.slice_len;
+    a.out_stride = f.key.cs;
+    a.njobs = (uint32_t)f.jobs.size();
+    a.sc = D.sc(f.key);
+    const DecJitGeom geo = dec_jit_geom(a.sc);  // the geometry the kernel was built for
+    a.wps = geo.wps;
+    a.wgs_per_stripe = geo.wgs;
+    a.n = (uint32_t)D.c->h.n;
+    a.nscratch = f.k->nscratch;
+    return a;
+}
+// Step 7: the call's workspace -- the table and pattern launches share one range (they run in
+// stream order), each class launch has its own after it (they may run side by side)
+int dec_scratch(DecCall &D) {
     // a small call (a per-call decode: a few stripes on a 256-CU chip) runs one wave per
     // workgroup, so each stripe's 100-step chain is split over more workgroups with less work per
     // step.  Measurement option TEC_DEBUG_KNOBS=1 TEC_DEC_SMALL=n: the stripe bound (0: never).
@@ -1834,160 +1617,150 @@ int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices
         const char *e = tec_knob("TEC_DEC_SMALL");
         return e ? (size_t)atoi(e) : kDecSmallStripes;
     }();
-    size_t call_stripes = 0;
-    for (auto &o : offs) call_stripes += groups[o.first].size();
-    for (const ClassGrp &cg : cls) call_stripes += cg.jobs.size();
     static const uint32_t class_g_big = [] {  // measurement option TEC_DEC_CLASS_G (1 or 2)
         const char *e = tec_knob("TEC_DEC_CLASS_G");
         return e && atoi(e) == 1 ? 1u : 2u;
     }();
-    const uint32_t class_g = call_stripes <= dec_small_max || (cls_small && small_dec_cls) ? 1u : class_g_big;
-    const bool small_dec = call_stripes <= dec_small_max;
-    auto dec_args = [&](const std::pair<uint64_t, size_t> &o) {
-        const uint64_t cs = o.first >> 32;
-        const uint32_t sc = (uint32_t)(cs / (uint64_t)h.alpha);
-        DecArgs a{};
-        a.jobs = A.at<GpeJob>(o.second);
-        if (in_store) {
-            a.patterns = c->dstore.pats.as<GpePattern>();
-            a.hdrs = c->dstore.hdrs.as<DecProgHdr>();
-            a.steps = c->dstore.steps.as<DecStepP>();
-            a.step_off = c->dstore.soff.as<uint32_t>();
-        } else {
-            a.patterns = A.at<GpePattern>(pat_off);
-            a.hdrs = A.at<DecProgHdr>(hdr_off);
-            a.steps = A.at<DecStepP>(step_off);
-            a.step_off = A.at<uint32_t>(soff_off);
-        }
-        a.njobs = (uint32_t)groups[o.first].size();
-        a.words_per_stripe = (sc + 3) / 4;
-        a.cs = (uint32_t)cs; a.sc = sc; a.n = (uint32_t)n; a.nk = (uint32_t)h.k;
-        a.lds_rows = lds_rows;
-        a.nscratch_max = nscr_max;
-        a.in_stride = group_in_stride[o.first];
-        a.out_stride = cs;
-        a.gmax = small_dec ? 1u : 0u;
-        return a;
-    };
-    auto fixed_args = [&](const Fixed &f, uint8_t *scratch) {
-        const uint64_t cs = f.key >> 32;
-        dfix_args a{};
-        a.jobs = reinterpret_cast<const dfix::Job *>(A.at<GpeJob>(f.off));
-        a.scratch = scratch;
-        a.in_stride = group_in_stride[f.key];
-        a.out_stride = cs;
-        a.njobs = (uint32_t)f.jobs.size();
-        a.sc = (uint32_t)(cs / (uint64_t)h.alpha);
-        const DecJitGeom geo = dec_jit_geom(a.sc);  // the geometry the kernel was built for
-        a.wps = geo.wps;
-        a.wgs_per_stripe = geo.wgs;
-        a.n = (uint32_t)n;
-        a.nscratch = f.k->nscratch;
-        return a;
-    };
+    size_t call_stripes = 0;
+    for (auto &o : D.offs) call_stripes += D.plan.groups.at(o.first).size();
+    for (const DecClassGrp &cg : D.route.cls) call_stripes += cg.jobs.size();
+    D.small_dec = call_stripes <= dec_small_max;
+    D.class_g = D.small_dec || D.route.cls_small ? 1u : class_g_big;
     size_t scratch_bytes = 0;
-    for (auto &o : offs)
-        if (staged_group(o.first)) scratch_bytes = std::max(scratch_bytes, decode_stage_scratch_bytes(dec_args(o)));
-    for (const Fixed &f : fixed) {
-        const dfix_args a = fixed_args(f, nullptr);
+    for (auto &o : D.offs)
+        if (D.staged_group(o.first)) scratch_bytes = std::max(scratch_bytes, decode_stage_scratch_bytes(dec_table_args(D, o)));
+    for (const DecFixed &f : D.fixed) {
+        const dfix_args a = dec_fixed_args(D, f);
         const DecJitGeom geo = dec_jit_geom(a.sc);
         const size_t b = (size_t)a.njobs * a.wgs_per_stripe * std::max(a.nscratch, 1u) * geo.G * 64u * geo.wb;
         scratch_bytes = std::max(scratch_bytes, b);
     }
-    // the class launches may run side by side: each its own scratch range, after the others'
     size_t cls_bytes = 0;
-    for (const ClassGrp &cg : cls) {
-        const uint32_t sc = (uint32_t)((cg.key >> 32) / (uint64_t)h.alpha);
-        cls_bytes += dec_class_scratch_bytes(cg.id, (uint32_t)cg.jobs.size(), sc, class_g);
-    }
+    for (const DecClassGrp &cg : D.route.cls)
+        cls_bytes += dec_class_scratch_bytes(cg.id, (uint32_t)cg.jobs.size(), D.sc(cg.key), D.class_g);
     const size_t cls_off = (scratch_bytes + 255) & ~(size_t)255;
     if (cls_bytes) scratch_bytes = cls_off + cls_bytes;
-    uint8_t *scratch = nullptr;
-    if (scratch_bytes) {
-        r = A.workspace(scratch_bytes, s, &scratch);
-        if (r) return r;
+    if (!scratch_bytes) return TE_OK;
+    const int r = D.c->dec.workspace(scratch_bytes, D.s, &D.scratch);
+    if (!r) D.cls_scratch = D.scratch + cls_off;
+    return r;
+}
+// The class groups side by side on up to 1 + kClsSide streams, largest first, each with its own
+// scratch range: one class's launch has a 100-step chain as its floor whatever its size, so
+// groups one after another leave the GPU idle at every tail
+int dec_launch_classes(DecCall &D) {
+    te_clay *c = D.c;
+    hipStream_t s = D.s;
+    te_decode_launch_stats &dls = c->dls;
+    const std::vector<DecClassGrp> &cls = D.route.cls;
+    const int ns = std::min<int>(D.class_streams, (int)cls.size());
+    std::vector<size_t> order(cls.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return cls[x].jobs.size() > cls[y].jobs.size(); });
+    hipStream_t ss[1 + te_clay::kClsSide] = {s};
+    if (ns > 1) {
+        if (!c->cls_fork) TE_HIP(hipEventCreateWithFlags(&c->cls_fork, hipEventDisableTiming));
+        TE_HIP(hipEventRecord(c->cls_fork, s));
+        for (int i = 1; i < ns; i++) {
+            if (!c->cls_s[i - 1]) TE_HIP(hipStreamCreateWithFlags(&c->cls_s[i - 1], hipStreamNonBlocking));
+            if (!c->cls_join[i - 1]) TE_HIP(hipEventCreateWithFlags(&c->cls_join[i - 1], hipEventDisableTiming));
+            TE_HIP(hipStreamWaitEvent(c->cls_s[i - 1], c->cls_fork, 0));
+            ss[i] = c->cls_s[i - 1];
+        }
     }
-    uint8_t *const cls_scratch = scratch ? scratch + cls_off : nullptr;
+    size_t scr_at = 0;
+    for (size_t k = 0; k < order.size(); k++) {
+        const DecClassGrp &cg = cls[order[k]];
+        const uint32_t sc = D.sc(cg.key);
+        TE_HIP(launch_dec_class(cg.id, c->dec.at<GpeJob>(cg.off), D.pats(), (uint32_t)cg.jobs.size(), sc, cg.key.slice_len,
+                                cg.key.cs, (uint32_t)c->h.n, D.cls_scratch + scr_at, D.class_g, ss[k % (size_t)ns]));
+        scr_at += dec_class_scratch_bytes(cg.id, (uint32_t)cg.jobs.size(), sc, D.class_g);
+        dls.class_launches[dec_class_base_id(cg.id)]++;  // a windowed kernel under its class
+        dls.class_stripes += cg.jobs.size();
+    }
+    dls.class_g = D.class_g;
+    dls.class_streams = std::max(dls.class_streams, (uint32_t)ns);
+    for (int i = 1; i < ns; i++) {
+        TE_HIP(hipEventRecord(c->cls_join[i - 1], ss[i]));
+        TE_HIP(hipStreamWaitEvent(s, c->cls_join[i - 1], 0));
+    }
+    return TE_OK;
+}
+// Step 8: gather, pattern kernels, class kernels, then each table group on the staged or the generic kernel
+int dec_launch(DecCall &D) {
+    te_clay *c = D.c;
+    const ClayHost &h = c->h;
+    hipStream_t s = D.s;
+    Arena &A = c->dec;
+    te_decode_launch_stats &dls = c->dls;  // summed: the calling entry point zeroed it
     KTimer kt(s);
-    if (!copies.empty()) TE_HIP(launch_gather(A.at<CopyJob>(copy_off), (uint32_t)copies.size(), s));
-    for (const Fixed &f : fixed) {
-        const dfix_args a = fixed_args(f, scratch);
+    if (!D.plan.copies.empty()) TE_HIP(launch_gather(A.at<CopyJob>(D.copy_off), (uint32_t)D.plan.copies.size(), s));
+    for (const DecFixed &f : D.fixed) {
+        const dfix_args a = dec_fixed_args(D, f);
         TE_HIP(launch_dec_fixed(*f.k, a, dec_jit_geom(a.sc).G, s));
         dls.jit_launches++;
         dls.jit_stripes += f.jobs.size();
     }
-    if (!cls.empty()) {
-        // the class groups side by side on up to 1 + kClsSide streams, largest first, each with
-        // its own scratch range: one class's launch has a 100-step chain as its floor whatever
-        // its size, so groups one after another leave the GPU idle at every tail
-        const int ns = std::min<int>(class_streams, (int)cls.size());
-        std::vector<size_t> order(cls.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return cls[x].jobs.size() > cls[y].jobs.size(); });
-        hipStream_t ss[1 + te_clay::kClsSide] = {s};
-        if (ns > 1) {
-            if (!c->cls_fork) TE_HIP(hipEventCreateWithFlags(&c->cls_fork, hipEventDisableTiming));
-            TE_HIP(hipEventRecord(c->cls_fork, s));
-            for (int i = 1; i < ns; i++) {
-                if (!c->cls_s[i - 1]) TE_HIP(hipStreamCreateWithFlags(&c->cls_s[i - 1], hipStreamNonBlocking));
-                if (!c->cls_join[i - 1]) TE_HIP(hipEventCreateWithFlags(&c->cls_join[i - 1], hipEventDisableTiming));
-                TE_HIP(hipStreamWaitEvent(c->cls_s[i - 1], c->cls_fork, 0));
-                ss[i] = c->cls_s[i - 1];
-            }
-        }
-        const GpePattern *pp = in_store ? c->dstore.pats.as<GpePattern>() : A.at<GpePattern>(pat_off);
-        size_t scr_at = 0;
-        for (size_t k = 0; k < order.size(); k++) {
-            const ClassGrp &cg = cls[order[k]];
-            const uint64_t cs = cg.key >> 32;
-            const uint32_t sc = (uint32_t)(cs / (uint64_t)h.alpha);
-            TE_HIP(launch_dec_class(cg.id, A.at<GpeJob>(cg.off), pp, (uint32_t)cg.jobs.size(), sc, group_in_stride[cg.key],
-                                    cs, (uint32_t)n, cls_scratch + scr_at, class_g, ss[k % (size_t)ns]));
-            scr_at += dec_class_scratch_bytes(cg.id, (uint32_t)cg.jobs.size(), sc, class_g);
-            dls.class_launches[dec_class_base_id(cg.id)]++;  // a windowed kernel under its class
-            dls.class_stripes += cg.jobs.size();
-        }
-        dls.class_g = class_g;
-        dls.class_streams = std::max(dls.class_streams, (uint32_t)ns);
-        for (int i = 1; i < ns; i++) {
-            TE_HIP(hipEventRecord(c->cls_join[i - 1], ss[i]));
-            TE_HIP(hipStreamWaitEvent(s, c->cls_join[i - 1], 0));
-        }
-    }
-    for (auto &o : offs) {
-        if (staged_group(o.first)) {
-            DecArgs a = dec_args(o);
-            a.scratch = scratch;
+    if (!D.route.cls.empty())
+        if (int r = dec_launch_classes(D)) return r;
+    for (auto &o : D.offs) {
+        if (D.staged_group(o.first)) {
+            DecArgs a = dec_table_args(D, o);
+            a.scratch = D.scratch;
             TE_HIP(launch_decode_stage(a, s));
             dls.table_launches++;
             dls.table_stripes += a.njobs;
             continue;
         }
-        const uint64_t cs = o.first >> 32;
-        const uint32_t sc = (uint32_t)(cs / (uint64_t)h.alpha);
+        const uint32_t sc = D.sc(o.first);
         const uint32_t wps = sc >= 4 ? (sc + 3) / 4 : 1;
         GpeArgs a{};
         a.jobs = A.at<GpeJob>(o.second);
-        a.patterns = A.at<GpePattern>(pat_off);
-        a.plane_pool = A.at<uint16_t>(pool_off);
-        a.njobs = (uint32_t)groups[o.first].size();
+        a.patterns = A.at<GpePattern>(D.pat_off);
+        a.plane_pool = A.at<uint16_t>(D.pool_off);
+        a.njobs = (uint32_t)D.plan.groups.at(o.first).size();
         a.word_base = 0;
         a.word_end = wps;
         a.groups_per_stripe = (wps + kGpeWords - 1) / kGpeWords;
-        a.cs = (uint32_t)cs; a.sc = sc; a.q = h.q; a.t = h.t; a.k = h.k; a.nu = h.nu; a.n = n; a.alpha = h.alpha;
-        a.in_stride = group_in_stride[o.first];
-        a.out_stride = cs;
-        a.in_rotated = rotated ? 1u : 0u;
+        a.cs = (uint32_t)o.first.cs; a.sc = sc; a.q = h.q; a.t = h.t; a.k = h.k; a.nu = h.nu; a.n = h.n; a.alpha = h.alpha;
+        a.in_stride = o.first.slice_len;
+        a.out_stride = o.first.cs;
+        a.in_rotated = D.rotated ? 1u : 0u;
         a.out_rotated = 0;
         a.out_mask = (h.k >= 64) ? ~0ull : ((1ull << h.k) - 1ull);
         for (int i = 0; i < 16; i++) a.qpow[i] = h.qpow[i];
-        TE_HIP(launch_gpe(a, max_er, s));
+        TE_HIP(launch_gpe(a, D.max_er, s));
         dls.generic_launches++;
         dls.generic_stripes += a.njobs;
     }
     kt.stop();
-    if (in_store) TE_HIP(c->dstore.readers.record(s));  // a later call that empties the store waits for these launches
+    if (D.in_store) TE_HIP(c->dstore.readers.record(s));  // a later call that empties the store waits for these launches
     return A.mark_done(s);
+}
+// Items with lost >= 0 (node recover) need the staged kernel: TE_ERR_UNSUPPORTED, before anything
+// is enqueued, when a pattern has no plane program (the caller then decodes and re-encodes).
+int decode_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const DecItem *items,
+                   size_t nitems, uint8_t *d_out, hipStream_t s, bool raw) {
+    static_assert(TE_DECODE_CLASSES == kDecClasses, "te_decode_launch_stats counts every class");
+    // compiled programs kept on the host: <= ~430 MB (26 KB per pattern, as many as the device
+    // store's cap; 77,520 masks exist for k = 7, x 20 outputs for node recover)
+    if (c->dec_cache.size() > std::max<size_t>(c->dstore.max_cap, nitems)) c->dec_cache.clear();
+    DecCall D{c, s, (cfg && !raw) ? cfg->rotated : 0};
+    D.plan = dec_plan(c->h, D.rotated, raw, items, nitems, d_slices, d_out);
+    const DecPlan &P = D.plan;
+    c->rgs.stripes_touched += P.touched; c->rgs.stripes_copied += P.copied; c->rgs.stripes_decoded += P.decoded;
+    c->rgs.gather_jobs += P.copies.size();
+    c->rcs.stripes_rebuilt += P.rebuilt; c->rcs.gather_jobs += P.chunk_gather; c->rcs.bytes_stored += P.bytes_stored;
+    if (P.groups.empty() && P.chunk_groups.empty())  // nothing to decode: a ranged call of copy stripes only (or of nothing)
+        return P.copies.empty() ? (int)TE_OK : gather_meta_enqueue(c->dec, s, P.copies, {});
+    int r = dec_resolve(D);
+    if (r) return r;
+    if (P.fused)
+        for (auto &kv : P.groups)
+            if (!D.staged_group(kv.first)) return TE_ERR_UNSUPPORTED;
+    dec_pick_jit(D);
+    if ((r = dec_route_call(D)) || (r = dec_image(D)) || (r = dec_upload(D)) || (r = dec_scratch(D))) return r;
+    return dec_launch(D);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3562,9 +3335,9 @@ int te_decode_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     return decode_enqueue(c, cfg, d_slices, items.data(), items.size(), d_out, (hipStream_t)stream, false);
 }
 
-int te_slicer_range_plan(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
-                         uint64_t start, uint64_t len, uint64_t *first_stripe, uint64_t *nstripes, uint32_t *classes,
-                         uint64_t *lo, uint64_t *hi) {
+int te_slicer_range_plan_ex(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
+                            uint64_t start, uint64_t len, int chunk_path, uint64_t *first_stripe, uint64_t *nstripes,
+                            uint32_t *classes, uint64_t *lo, uint64_t *hi, uint32_t *shards) {
     if (!c || !cfg || !first_stripe || !nstripes) return TE_ERR_INVALID_ARG;
     const ClayHost &h = c->h;
     if (!range_valid(blob_len, start, len)) return TE_ERR_INVALID_ARG;
@@ -3577,35 +3350,22 @@ int te_slicer_range_plan(const te_clay *c, const te_slicer_cfg *cfg, uint64_t bl
     range_stripes(g.stripe_size, start, len, sb, se);
     *first_stripe = sb;
     *nstripes = se - sb;
+    const bool chunk_ok = chunk_path && range_chunk_ok(h, g.chunk_size, g.slice_len);
     for (uint64_t st = sb; st < se; st++) {
         const RangeWin w = range_window(h.n, cfg->rotated, avail, blob_len, g.stripe_size, g.chunk_size, st, start, len);
-        if (classes) classes[st - sb] = w.copy ? TE_RANGE_COPY : TE_RANGE_DECODE;
+        const bool chunk = chunk_ok && w.miss == 1;
+        if (classes) classes[st - sb] = chunk ? TE_RANGE_CHUNK : w.copy ? TE_RANGE_COPY : TE_RANGE_DECODE;
         if (lo) lo[st - sb] = w.lo;
         if (hi) hi[st - sb] = w.hi;
+        if (shards) shards[st - sb] = chunk ? w.miss_x : UINT32_MAX;
     }
     return TE_OK;
 }
 
-int te_slicer_range_plan_ex(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
-                            uint64_t start, uint64_t len, int chunk_path, uint64_t *first_stripe, uint64_t *nstripes,
-                            uint32_t *classes, uint64_t *lo, uint64_t *hi, uint32_t *shards) {
-    int r = te_slicer_range_plan(c, cfg, blob_len, avail_mask, start, len, first_stripe, nstripes, classes, lo, hi);
-    if (r) return r;
-    for (uint64_t i = 0; shards && i < *nstripes; i++) shards[i] = UINT32_MAX;
-    if (!chunk_path || *nstripes == 0) return TE_OK;
-    const ClayHost &h = c->h;
-    te_geometry g;
-    if ((r = te_slicer_geometry(c, (size_t)blob_len, &g))) return r;
-    if (!range_chunk_ok(h, g.chunk_size, g.slice_len)) return TE_OK;
-    const uint32_t avail = avail_mask & (h.n >= 32 ? 0xffffffffu : (1u << h.n) - 1u);
-    for (uint64_t i = 0; i < *nstripes; i++) {
-        const RangeWin w = range_window(h.n, cfg->rotated, avail, blob_len, g.stripe_size, g.chunk_size, *first_stripe + i,
-                                        start, len);
-        if (w.miss != 1) continue;
-        if (classes) classes[i] = TE_RANGE_CHUNK;
-        if (shards) shards[i] = w.miss_x;
-    }
-    return TE_OK;
+int te_slicer_range_plan(const te_clay *c, const te_slicer_cfg *cfg, uint64_t blob_len, uint32_t avail_mask,
+                         uint64_t start, uint64_t len, uint64_t *first_stripe, uint64_t *nstripes, uint32_t *classes,
+                         uint64_t *lo, uint64_t *hi) {
+    return te_slicer_range_plan_ex(c, cfg, blob_len, avail_mask, start, len, 0, first_stripe, nstripes, classes, lo, hi, nullptr);
 }
 
 int te_clay_set_range_chunk_path(te_clay *c, int on) {
@@ -3682,6 +3442,14 @@ int te_repair_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair
 // shard are re-encoded.  Objects go through the device workspaces in windows (bounded memory);
 // the workspaces are ordered against a previous call on another stream by `rec_done`.
 }  // extern "C"
+// later calls (any stream) order against everything this one enqueued on s
+static int rec_mark_done(te_clay *c, hipStream_t s) {
+    if (!c->rec_done) TE_HIP(hipEventCreateWithFlags(&c->rec_done, hipEventDisableTiming));
+    const int r = hip_status(hipEventRecord(c->rec_done, s));
+    c->rec_pending = true;
+    c->rec_stream = s;
+    return r;
+}
 // part = a subset of a mixed batch, called from the whole batch's call: the launch stats go on summing
 // locked = the caller holds the handle's lock (the host rebuild pipeline)
 static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_object *objs,
@@ -3717,17 +3485,22 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
         chunk[i] = g.chunk_size;
         for (int w = 0; w < 6; w++) meta_w[i * 6 + w] = get_u64(h_meta + i * TE_META_SIZE + 8 * w);
     }
-    // A mixed batch goes in two parts: the objects the fused path takes (a plane-program profile,
-    // sub-chunks of >= 8 bytes, 31-bit slice offsets: decode_enqueue's staged_group) and the rest,
+    auto meta_job = [&](size_t i, uint8_t *dst) {  // object i's metadata suffix, written at dst
+        MetaJob m{};
+        m.dst = dst;
+        for (int k = 0; k < 6; k++) m.words[k] = meta_w[i * 6 + k];
+        return m;
+    };
+    // A mixed batch goes in two parts: the objects the fused path takes (a plane-program profile
+    // and a geometry the staged kernels address: dec_geom_staged) and the rest,
     // so one small object does not send the whole batch to the windowed decode + re-encode
     // (ADVICE r03).  Offsets are absolute, so each part is the same call on a subset.
     {
         const bool planes = h.q == kRepQ && h.t == 2 && h.nu == 0;
         std::vector<size_t> part[2];
         for (size_t i = 0; i < nobj; i++) {
-            const uint64_t sc = chunk[i] / (uint64_t)h.alpha;
-            const bool fz = planes && (items[i].ns == 0 || sc >= 8) && (uint64_t)n * objs[i].slice_len < 0x7fffffffull &&
-                            chunk[i] * (uint64_t)h.k < 0x7fffffffull;
+            // (an empty blob has no stripe to decode: its one all-zero chunk is short)
+            const bool fz = planes && (items[i].ns == 0 || dec_geom_staged(h, chunk[i], objs[i].slice_len));
             part[fz ? 0 : 1].push_back(i);
         }
         if (!part[0].empty() && !part[1].empty()) {
@@ -3757,11 +3530,7 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
             fi[i].out_off = objs[i].out_off;
             uint8_t *dst = d_out + objs[i].out_off;
             if (items[i].ns == 0) zeros.push_back(CopyJob{d_out, dst, chunk[i] * nstripes[i], 0});
-            MetaJob m{};
-            m.dst = dst + nstripes[i] * chunk[i];
-            m.slice_len = 0;
-            for (int k = 0; k < 6; k++) m.words[k] = meta_w[i * 6 + k];
-            metas.push_back(m);
+            metas.push_back(meta_job(i, dst + nstripes[i] * chunk[i]));
         }
         std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
         if (!locked) lk.lock();
@@ -3771,22 +3540,8 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
         const int rf = decode_enqueue(c, cfg, d_slices, fi.data(), nobj, d_out, s, false);
         if (rf != TE_ERR_UNSUPPORTED) {
             if (rf) return rf;
-            Arena &A = c->rec;
             if (c->rec_pending && c->rec_stream != s) TE_HIP(hipStreamWaitEvent(s, c->rec_done, 0));
-            A.img.clear();
-            const size_t zoff = A.put(zeros.data(), zeros.size() * sizeof(CopyJob));
-            const size_t moff = A.put(metas.data(), metas.size() * sizeof(MetaJob));
-            int r = A.upload(s);
-            if (r) return r;
-            KTimer kt(s);
-            if (!zeros.empty()) TE_HIP(launch_gather(A.at<CopyJob>(zoff), (uint32_t)zeros.size(), s));
-            TE_HIP(launch_meta(A.at<MetaJob>(moff), (uint32_t)metas.size(), 1u, s));
-            kt.stop();
-            r = A.mark_done(s);
-            if (!c->rec_done) TE_HIP(hipEventCreateWithFlags(&c->rec_done, hipEventDisableTiming));
-            const int r2 = hip_status(hipEventRecord(c->rec_done, s));
-            c->rec_pending = true;
-            c->rec_stream = s;
+            const int r = gather_meta_enqueue(c->rec, s, zeros, metas), r2 = rec_mark_done(c, s);
             return r ? r : r2;
         }
     }
@@ -3823,7 +3578,6 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     hipStream_t s = (hipStream_t)stream;
-    if (!c->rec_done) TE_HIP(hipEventCreateWithFlags(&c->rec_done, hipEventDisableTiming));
     if (max_blob > c->rec_blob.cap || max_slices > c->rec_slices.cap) {
         if (c->rec_pending) TE_HIP(hipEventSynchronize(c->rec_done));  // queued work may still use them
     } else if (c->rec_pending && c->rec_stream != s) {
@@ -3887,27 +3641,11 @@ static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_
                     jobs.push_back(CopyJob{blob + blob_off[i - w.b] + std::min(start, it.blob_len), dst + st * cs, cs, valid});
                 }
             }
-            MetaJob m{};
-            m.dst = dst + ns * cs;
-            m.slice_len = 0;
-            for (int k = 0; k < 6; k++) m.words[k] = meta_w[i * 6 + k];
-            metas.push_back(m);
+            metas.push_back(meta_job(i, dst + ns * cs));
         }
-        Arena &A = c->rec;
-        A.img.clear();
-        const size_t off = A.put(jobs.data(), jobs.size() * sizeof(CopyJob));
-        const size_t moff = A.put(metas.data(), metas.size() * sizeof(MetaJob));
-        if ((r = A.upload(s))) break;
-        KTimer kt(s);
-        if ((r = hip_status(launch_gather(A.at<CopyJob>(off), (uint32_t)jobs.size(), s)))) break;
-        if ((r = hip_status(launch_meta(A.at<MetaJob>(moff), (uint32_t)metas.size(), 1u, s)))) break;
-        kt.stop();
-        if ((r = A.mark_done(s))) break;
+        if ((r = gather_meta_enqueue(c->rec, s, jobs, metas))) break;
     }
-    // later calls (any stream) order against everything this one enqueued
-    const int r2 = hip_status(hipEventRecord(c->rec_done, s));
-    c->rec_pending = true;
-    c->rec_stream = s;
+    const int r2 = rec_mark_done(c, s);
     return r ? r : r2;
 }
 extern "C" {
@@ -3981,8 +3719,10 @@ int te_clay_encode(te_clay *c, const uint8_t *data, size_t len, uint8_t *chunks,
 // path outruns the 4-thread memcpy there (7 x 11.4 MB, 64 MiB object: 3.03 ms direct, 4.2-4.5
 // gathered).
 constexpr size_t kGatherMaxSlice = 2u << 20;
-static int upload_slices(te_clay *c, const uint8_t *const *slices, size_t len) {
+static int upload_slices(te_clay *c, const uint8_t *const *slices, size_t len, size_t out_bytes) {
     const int n = c->h.n;
+    TE_HIP(c->io_in.ensure((size_t)n * len));
+    TE_HIP(c->io_out.ensure(out_bytes));  // (both buffers before the first copy is queued)
     const uint8_t *src[64];
     int gather = 0;
     for (int i = 0; i < n; i++) {
@@ -4005,16 +3745,58 @@ static int upload_slices(te_clay *c, const uint8_t *const *slices, size_t len) {
                                   c->stream));
     return TE_OK;
 }
+// The present ones of n slice pointers (null = absent) as a mask; *first: the lowest, or -1
+static uint32_t slices_avail(const uint8_t *const *slices, int n, int *first = nullptr) {
+    uint32_t avail = 0;
+    for (int i = 0; i < n; i++)
+        if (slices[i]) avail |= 1u << i;
+    if (first) *first = avail ? __builtin_ctz(avail) : -1;
+    return avail;
+}
+// Measurement option TEC_DEBUG_KNOBS=1 TEC_DECODE_ZC=0: the per-call decodes' device copies instead
+static bool decode_zc() {
+    static const bool zc = [] { const char *e = tec_knob("TEC_DECODE_ZC"); return !(e && e[0] == '0'); }();
+    return zc;
+}
+// A per-call decode (<= 64 stripes, the one-wave class kernels) reads its slices from page-locked
+// host staging and writes the object to page-locked memory over PCIe, with no H2D / D2H copy around
+// a 0.3 ms kernel whose loader wave issues its loads four steps ahead.  slices: gathered into the
+// staging at i * len by the copy pool (the repair call's scheme); null: the caller staged them.  A
+// page-locked `out` is written at its device address; otherwise the `bytes` of output are staged.
+static int percall_decode_pinned(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t len,
+                                 const DecItem &it, uint8_t *out, size_t bytes, bool raw) {
+    if (slices) {
+        TE_HIP(c->hio_in.ensure((size_t)c->h.n * len));
+        std::vector<tec::CopyPool::Seg> segs;
+        for (int i = 0; i < c->h.n; i++)
+            if (slices[i]) segs.push_back({c->hio_in.u8() + (size_t)i * len, slices[i], len});
+        copy_pool(c->device).run(segs);
+    }
+    uint8_t *const d_out = host_device_ptr(out);
+    if (!d_out) TE_HIP(c->hio_out.ensure(bytes));
+    const int r = decode_enqueue(c, cfg, c->hio_in.u8(), &it, 1, d_out ? d_out : c->hio_out.u8(), c->stream, raw);
+    if (r) return r;
+    TE_HIP(hipStreamSynchronize(c->stream));
+    if (!d_out) copy_pool(c->device).run({{out, c->hio_out.p, bytes}});
+    c->dls.direct_out = d_out ? 1u : 0u;
+    return TE_OK;
+}
+// ... or through device copies: the slices are in c->io_in, `bytes` of output come back from c->io_out
+static int percall_decode_device(te_clay *c, const te_slicer_cfg *cfg, const DecItem &it, uint8_t *out, size_t bytes, bool raw) {
+    TE_HIP(c->io_out.ensure(bytes));
+    const int r = decode_enqueue(c, cfg, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, raw);
+    if (r) return r;
+    TE_HIP(hipMemcpyAsync(out, c->io_out.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    TE_HIP(hipStreamSynchronize(c->stream));
+    return TE_OK;
+}
 extern "C" {
 
 int te_clay_decode(te_clay *c, const uint8_t *const *chunks, size_t cs, uint8_t *out, size_t cap) {
     if (!c || !chunks || !out) return TE_ERR_INVALID_ARG;
     const ClayHost &h = c->h;
-    uint32_t avail = 0;
-    int na = 0;
-    for (int i = 0; i < h.n; i++)
-        if (chunks[i]) { avail |= 1u << i; na++; }
-    if (na < h.k) return TE_ERR_NOT_ENOUGH_SLICES;  // clay.rs:107-109
+    const uint32_t avail = slices_avail(chunks, h.n);
+    if (__builtin_popcount(avail) < h.k) return TE_ERR_NOT_ENOUGH_SLICES;  // clay.rs:107-109
     if (cs == 0 || cs % (size_t)h.alpha) return TE_ERR_BAD_ENCODING;
     if (cap < (size_t)h.k * cs) return TE_ERR_BUFFER_TOO_SMALL;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -4023,48 +3805,21 @@ int te_clay_decode(te_clay *c, const uint8_t *const *chunks, size_t cs, uint8_t 
     TE_HIP(dg.err);
     int r = ensure_stream(c);
     if (r) return r;
-    const size_t total = (size_t)h.n * cs;
     DecItem it{};
     it.in_base = 0; it.slice_len = cs; it.blob_len = (uint64_t)h.k * cs; it.stripe = it.blob_len; it.ns = 1; it.cs = cs;
     it.out_off = 0; it.avail = avail;
     // one stripe: the zero-copy per-call path of te_slicer_decode (staging read and written over PCIe)
-    static const bool zc = [] { const char *e = tec_knob("TEC_DECODE_ZC"); return !(e && e[0] == '0'); }();
-    if (zc) {
-        TE_HIP(c->hio_in.ensure(total));
-        std::vector<tec::CopyPool::Seg> segs;
-        for (int i = 0; i < h.n; i++)
-            if (chunks[i]) segs.push_back({c->hio_in.u8() + (size_t)i * cs, chunks[i], cs});
-        copy_pool(c->device).run(segs);
-        // a page-locked `out` is written by the kernels at its device address; otherwise staged
-        uint8_t *const d_out = host_device_ptr(out);
-        if (!d_out) TE_HIP(c->hio_out.ensure((size_t)h.k * cs));
-        uint8_t *dst = d_out ? d_out : c->hio_out.u8();
-        r = decode_enqueue(c, nullptr, c->hio_in.u8(), &it, 1, dst, c->stream, true);
-        if (r) return r;
-        TE_HIP(hipStreamSynchronize(c->stream));
-        if (!d_out) copy_pool(c->device).run({{out, c->hio_out.p, (size_t)h.k * cs}});
-        c->dls.direct_out = d_out ? 1u : 0u;
-        return TE_OK;
-    }
-    TE_HIP(c->io_in.ensure(total));
-    TE_HIP(c->io_out.ensure((size_t)h.k * cs));
-    r = upload_slices(c, chunks, cs);
-    if (r) return r;
-    r = decode_enqueue(c, nullptr, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, true);
-    if (r) return r;
-    TE_HIP(hipMemcpyAsync(out, c->io_out.p, (size_t)h.k * cs, hipMemcpyDeviceToHost, c->stream));
-    TE_HIP(hipStreamSynchronize(c->stream));
-    return TE_OK;
+    if (decode_zc()) return percall_decode_pinned(c, nullptr, chunks, cs, it, out, (size_t)h.k * cs, true);
+    if ((r = upload_slices(c, chunks, cs, (size_t)h.k * cs))) return r;
+    return percall_decode_device(c, nullptr, it, out, (size_t)h.k * cs, true);
 }
 
 int te_slicer_decode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
                      uint8_t *out, size_t cap, size_t *out_len) {
     if (!c || !cfg || !slices) return TE_ERR_INVALID_ARG;
     const ClayHost &h = c->h;
-    uint32_t avail = 0;
-    int first = -1;
-    for (int i = 0; i < h.n; i++)
-        if (slices[i]) { avail |= 1u << i; if (first < 0) first = i; }
+    int first;
+    const uint32_t avail = slices_avail(slices, h.n, &first);
     if (first < 0) return TE_ERR_NOT_ENOUGH_SLICES;
     if (slice_len < TE_META_SIZE) return TE_ERR_INVALID_LAYOUT;
     DecItem it{};
@@ -4079,40 +3834,11 @@ int te_slicer_decode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const 
     TE_HIP(dg.err);
     r = ensure_stream(c);
     if (r) return r;
-    const size_t total = (size_t)h.n * slice_len;
     it.in_base = 0;
     it.out_off = 0;
-    // A per-call decode (<= 64 stripes, the one-wave class kernels) reads its slices from page-
-    // locked host staging and writes the object to page-locked memory over PCIe, with no H2D /
-    // D2H copy around a 0.3 ms kernel whose loader wave issues its loads four steps ahead; the
-    // slices are gathered into the staging by the copy pool (the repair call's scheme).
-    // Measurement option TEC_DEBUG_KNOBS=1 TEC_DECODE_ZC=0: the copies instead.
-    static const bool zc = [] { const char *e = tec_knob("TEC_DECODE_ZC"); return !(e && e[0] == '0'); }();
-    if (zc && it.ns <= kDecSmallStripes) {
-        TE_HIP(c->hio_in.ensure(total));
-        std::vector<tec::CopyPool::Seg> segs;
-        for (int i = 0; i < h.n; i++)
-            if (slices[i]) segs.push_back({c->hio_in.u8() + (size_t)i * slice_len, slices[i], slice_len});
-        copy_pool(c->device).run(segs);
-        uint8_t *const d_out = host_device_ptr(out);  // page-locked: its device address; else staged
-        if (!d_out) TE_HIP(c->hio_out.ensure(it.blob_len));
-        uint8_t *dst = d_out ? d_out : c->hio_out.u8();
-        r = decode_enqueue(c, cfg, c->hio_in.u8(), &it, 1, dst, c->stream, false);
-        if (r) return r;
-        TE_HIP(hipStreamSynchronize(c->stream));
-        if (!d_out) copy_pool(c->device).run({{out, c->hio_out.p, it.blob_len}});
-        c->dls.direct_out = d_out ? 1u : 0u;
-        return TE_OK;
-    }
-    TE_HIP(c->io_in.ensure(total));
-    TE_HIP(c->io_out.ensure(it.blob_len));
-    r = upload_slices(c, slices, slice_len);
-    if (r) return r;
-    r = decode_enqueue(c, cfg, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, false);
-    if (r) return r;
-    TE_HIP(hipMemcpyAsync(out, c->io_out.p, it.blob_len, hipMemcpyDeviceToHost, c->stream));
-    TE_HIP(hipStreamSynchronize(c->stream));
-    return TE_OK;
+    if (decode_zc() && it.ns <= kDecSmallStripes) return percall_decode_pinned(c, cfg, slices, slice_len, it, out, it.blob_len, false);
+    if ((r = upload_slices(c, slices, slice_len, it.blob_len))) return r;
+    return percall_decode_device(c, cfg, it, out, it.blob_len, false);
 }
 
 int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
@@ -4120,10 +3846,8 @@ int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     if (!c || !cfg || !slices) return TE_ERR_INVALID_ARG;
     const ClayHost &h = c->h;
     const int n = h.n;
-    uint32_t avail = 0;
-    int first = -1;
-    for (int i = 0; i < n; i++)
-        if (slices[i]) { avail |= 1u << i; if (first < 0) first = i; }
+    int first;
+    const uint32_t avail = slices_avail(slices, n, &first);
     if (first < 0) return TE_ERR_NOT_ENOUGH_SLICES;
     if (slice_len < TE_META_SIZE) return TE_ERR_INVALID_LAYOUT;
     DecItem it{};
@@ -4193,26 +3917,12 @@ int te_slicer_decode_range(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *
     copy_pool(c->device).run(segs);
     // few stripes: the kernels read the page-locked staging and write a page-locked `out` over
     // PCIe, as te_slicer_decode does; more: the staged pieces go to device memory first
-    if (se - sb <= kDecSmallStripes) {
-        uint8_t *const d_out = host_device_ptr(out);
-        if (!d_out) TE_HIP(c->hio_out.ensure(len));
-        uint8_t *dst = d_out ? d_out : c->hio_out.u8();
-        r = decode_enqueue(c, cfg, c->hio_in.u8(), &it, 1, dst, c->stream, false);
-        if (r) return r;
-        TE_HIP(hipStreamSynchronize(c->stream));
-        if (!d_out) copy_pool(c->device).run({{out, c->hio_out.p, (size_t)len}});
-        c->dls.direct_out = d_out ? 1u : 0u;
-        return TE_OK;
-    }
+    if (se - sb <= kDecSmallStripes) return percall_decode_pinned(c, cfg, nullptr, 0, it, out, (size_t)len, false);
     TE_HIP(c->io_in.ensure(total));
     TE_HIP(c->io_out.ensure(len));
     for (const Piece &p : pieces)
         TE_HIP(hipMemcpyAsync(c->io_in.as<uint8_t>() + p.at, c->hio_in.u8() + p.at, p.len, hipMemcpyHostToDevice, c->stream));
-    r = decode_enqueue(c, cfg, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, false);
-    if (r) return r;
-    TE_HIP(hipMemcpyAsync(out, c->io_out.p, len, hipMemcpyDeviceToHost, c->stream));
-    TE_HIP(hipStreamSynchronize(c->stream));
-    return TE_OK;
+    return percall_decode_device(c, cfg, it, out, (size_t)len, false);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -5136,9 +4846,8 @@ int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_
     if (!c || !cfg || !slices || !leaves) return TE_ERR_INVALID_ARG;
     const ClayHost &h = c->h;
     const int n = h.n;
-    uint32_t avail = 0, good = 0;
-    for (int i = 0; i < n; i++)
-        if (slices[i]) avail |= 1u << i;
+    uint32_t good = 0;
+    const uint32_t avail = slices_avail(slices, n);
     if (!avail) return TE_ERR_NOT_ENOUGH_SLICES;
     if (slice_len < TE_META_SIZE) return TE_ERR_INVALID_LAYOUT;
     // one call's 7..20 slices: a host core with the SHA extensions hashes a slice about as fast as
@@ -5181,8 +4890,7 @@ int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_
     int r = ensure_stream(c);
     if (r) return r;
     // the slices go up once: the kernel hashes them in the staging the decode then reads
-    TE_HIP(c->io_in.ensure((size_t)n * slice_len));
-    if ((r = upload_slices(c, slices, slice_len))) return r;
+    if ((r = upload_slices(c, slices, slice_len, 0))) return r;
     std::vector<te_verify_item> vi;
     verify_push_slices(vi, 0, (uint32_t)n, 0, slice_len, avail);
     if ((r = verify_wait(c, c->io_in.as<uint8_t>(), vi, leaves, (size_t)n, 1, &good, c->stream))) return r;
@@ -5195,11 +4903,7 @@ int te_slicer_decode_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_
     if (!out || cap < it.blob_len) return TE_ERR_BUFFER_TOO_SMALL;
     it.in_base = 0;
     it.out_off = 0;
-    TE_HIP(c->io_out.ensure(it.blob_len));
-    if ((r = decode_enqueue(c, cfg, c->io_in.as<uint8_t>(), &it, 1, c->io_out.as<uint8_t>(), c->stream, false))) return r;
-    TE_HIP(hipMemcpyAsync(out, c->io_out.p, it.blob_len, hipMemcpyDeviceToHost, c->stream));
-    TE_HIP(hipStreamSynchronize(c->stream));
-    return TE_OK;
+    return percall_decode_device(c, cfg, it, out, it.blob_len, false);
 }
 
 }  // extern "C"

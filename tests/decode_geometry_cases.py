@@ -17,7 +17,7 @@ N = 20
 Q = 10            # the table kernel's profiles: q = 10, t = 2, alpha = 100
 ALPHA = 100
 STRIPES = (100_000, 1_000_000, 10_000_000)
-SMALL_STRIPES = 64  # engine.cpp kDecSmallStripes: a call of at most this many stripes runs G = 1
+SMALL_STRIPES = 64  # dec_plan.hpp kDecSmallStripes: a call of at most this many stripes runs G = 1
 MAXG = 2            # decode_stage.hip TEC_DEC_MAXG
 
 
