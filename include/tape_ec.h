@@ -540,6 +540,52 @@ int te_recover_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t 
                             const te_recover_object *objs, const uint8_t *h_meta, size_t nobj,
                             uint8_t *d_out, void *hip_stream);
 
+/* Several lost slices of one object from one decode: `reconstruct` (recover.rs:411-442) decodes
+ * k peer slices, re-encodes all n and keeps one; a node that owns L spools of a group, or a
+ * gateway healing an object it has just read, wants L of them from the same k peers. */
+typedef struct te_recover_multi_object {
+    uint64_t slices_off, slice_len; /* peer slice i at d_slices + slices_off + i*slice_len */
+    uint32_t avail_mask;   /* >= k bits */
+    uint32_t lost_mask;    /* 1..n-k bits, disjoint from avail_mask */
+    uint64_t out_off;      /* rebuilt slices, ascending slice index, packed:
+                              j-th set bit of lost_mask at d_out + out_off + j*slice_len */
+} te_recover_multi_object;
+/* Batched multi-slice node recover.  Every rebuilt slice is what te_recover_batch_device writes
+ * for that slice: its chunks, then the 48-byte suffix of h_meta (the peers' chunk_index).  The
+ * survivors are the decode's (the absent shards padded to n - k erasures: of more than k
+ * available slices the decode's k are read).  An object with one lost slice runs
+ * te_recover_batch_device's path unchanged; two or more run one multi-output kernel pass per
+ * stripe -- or a few, when the lost set is split to fit the kernel -- on q = 10, t = 2 profiles
+ * (n = 20), and the decode + re-encode on any other.  out_off has no alignment rule.
+ * TE_ERR_INVALID_ARG: lost_mask zero, a bit at or above n, more than n - k bits, or a bit of
+ * avail_mask; TE_ERR_NOT_ENOUGH_SLICES below k available slices; the layout errors of
+ * te_recover_batch_device for a suffix or slice length that does not validate.  An empty blob's
+ * slices are one zero chunk and the suffix. */
+int te_recover_multi_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                  const te_recover_multi_object *objs, const uint8_t *h_meta, size_t nobj,
+                                  uint8_t *d_out, void *hip_stream);
+/* One object, HOST -> HOST: slices[i] is slice i (slice_len bytes) or NULL; the present ones go up
+ * once (pageable or page-locked), out[j] receives the j-th set bit of lost_mask (slice_len bytes).
+ * A lost bit whose slice is present is TE_ERR_INVALID_ARG.  Synchronous. */
+int te_slicer_recover_multi(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices,
+                            size_t slice_len, uint32_t lost_mask, uint8_t *const *out);
+/* The handle's last te_recover_multi_batch_device / te_slicer_recover_multi call, zeroed when the
+ * call has passed its argument checks (host bookkeeping only).  The single-slice and generic
+ * objects' kernels are in te_clay_decode_launch_stats / te_clay_encode_launch_stats. */
+typedef struct te_recover_multi_stats {
+    uint32_t multi_launches;   /* launches of the multi-output kernel (one per chunk size and slice length) */
+    uint32_t passes;           /* most passes any stripe took: 1, or its sub-masks after a split (0: no launch) */
+    uint64_t jobs;             /* (stripe, sub-mask) jobs of those launches */
+    uint64_t out_rows;      /* output rows they stored: alpha per (stripe, lost node) */
+    uint64_t stripes;          /* stripes of the multi-kernel objects */
+    uint64_t split_stripes;    /* of those, stripes whose lost set was split */
+    uint64_t single_objects;   /* objects sent to the single-slice path (one lost slice, or an empty blob) */
+    uint64_t generic_objects;  /* objects decoded and re-encoded (profiles without plane programs,
+                                  sub-chunks below 8 bytes, slices past the 31-bit offset limit) */
+    uint64_t multi_objects;    /* objects on the multi-output kernel */
+} te_recover_multi_stats;
+int te_clay_recover_multi_launch_stats(te_clay *c, te_recover_multi_stats *out);
+
 /* ------------------------------------------------------------------------------------------
  * Slice commitments: BlobEncoder::encode_with_proofs' step after encode
  * (sdk/src/codec/encoder.rs:226-234) -- hash_leaf per slice, the merkle root and a proof per

@@ -91,6 +91,45 @@ pub fn recover_batch(coder: &mut ClayCoder, cfg: &ObjectCfg, slices: &PinnedBuf,
     Ok((0..objects.len()).map(|i| RecoverOutcome { status: st[i], rejected_mask: rej[i], verified: ok[i] != 0 }).collect())
 }
 
+/// te_slicer_recover_multi: `reconstruct` (recover.rs:411-442) for several lost slices of one
+/// object.  A node that owns L spools of a group rebuilds them from one fetch of k peer slices: the
+/// slices go to the device once, one decode rebuilds every slice index in `lost`.  Returns
+/// (slice index, slice) in ascending index order.  A lost index whose slice is present, or none, is
+/// the call's error.
+pub fn recover_many(coder: &mut ClayCoder, cfg: &ObjectCfg, slices: &[(usize, &[u8])], lost: &[usize])
+        -> Result<Vec<(usize, Vec<u8>)>, DecodeError> {
+    let n = coder.n();
+    if slices.is_empty() { return Err(DecodeError::NotEnoughSlices) }
+    let slen = slices[0].1.len();
+    let mut ptrs = vec![std::ptr::null::<u8>(); n];
+    for (i, s) in slices {
+        if *i >= n || s.len() != slen || !ptrs[*i].is_null() { return Err(DecodeError::InvalidLayout) }
+        ptrs[*i] = s.as_ptr();
+    }
+    let mut want: Vec<usize> = lost.to_vec();
+    want.sort_unstable();
+    want.dedup();
+    assert!(!want.is_empty() && want.len() == lost.len() && want.iter().all(|&i| i < n), "lost: distinct slice indices below n");
+    let mask = want.iter().fold(0u32, |m, &i| m | 1u32 << i);
+    let mut outs: Vec<Vec<u8>> = want.iter().map(|_| vec![0u8; slen]).collect();
+    let optrs: Vec<*mut u8> = outs.iter_mut().map(|o| o.as_mut_ptr()).collect();
+    let c = cfg.ffi();
+    decode_status(unsafe {
+        ffi::te_slicer_recover_multi(coder.raw.as_ptr(), &c, ptrs.as_ptr(), slen, mask, optrs.as_ptr())
+    })?;
+    Ok(want.into_iter().zip(outs).collect())
+}
+
+/// The last `recover_many` call on this coder: launches of the multi-output kernel, the most
+/// passes a stripe took, its jobs and output rows, and the objects sent to each path.
+pub fn recover_many_launch_stats(coder: &ClayCoder) -> ffi::te_recover_multi_stats {
+    let mut st = ffi::te_recover_multi_stats { multi_launches: 0, passes: 0, jobs: 0, out_rows: 0, stripes: 0,
+                                               split_stripes: 0, single_objects: 0, generic_objects: 0, multi_objects: 0 };
+    let s = unsafe { ffi::te_clay_recover_multi_launch_stats(coder.raw.as_ptr(), &mut st) };
+    if s != 0 { fatal(s) }
+    st
+}
+
 /// The last `repair_batch` / `recover_batch` call on this coder: windows, objects, fragments or
 /// slices and bytes uploaded, bytes copied back, where the leaves were hashed, host waits.
 pub fn rebuild_launch_stats(coder: &ClayCoder) -> ffi::te_rebuild_launch_stats {

@@ -90,6 +90,17 @@ class te_recover_object(C.Structure):
                 ("lost", C.c_uint32), ("out_off", C.c_uint64)]
 
 
+class te_recover_multi_object(C.Structure):
+    _fields_ = [("slices_off", C.c_uint64), ("slice_len", C.c_uint64), ("avail_mask", C.c_uint32),
+                ("lost_mask", C.c_uint32), ("out_off", C.c_uint64)]
+
+
+class te_recover_multi_stats(C.Structure):
+    _fields_ = [("multi_launches", C.c_uint32), ("passes", C.c_uint32)] + \
+               [(f, C.c_uint64) for f in ("jobs", "out_rows", "stripes", "split_stripes", "single_objects",
+                                          "generic_objects", "multi_objects")]
+
+
 class te_repair_object(C.Structure):
     _fields_ = [("plan", C.c_void_p), ("helper_off", C.c_uint64 * 20), ("out_off", C.c_uint64),
                 ("metadata", C.c_uint8 * 48)]
@@ -275,6 +286,10 @@ def _load() -> C.CDLL:
         "te_repair_batch_device": (i, [vp, vp, C.POINTER(te_repair_object), sz, vp, vp]),
         "te_recover_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_object), u8p, sz,
                                         vp, vp]),
+        "te_recover_multi_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_multi_object), u8p,
+                                              sz, vp, vp]),
+        "te_slicer_recover_multi": (i, [vp, C.POINTER(te_slicer_cfg), pp, sz, u32, pp]),
+        "te_clay_recover_multi_launch_stats": (i, [vp, C.POINTER(te_recover_multi_stats)]),
         "te_hash_leaf": (i, [u8p, sz, u8p]),
         "te_hash_leaves": (i, [u8p, sz, sz, u32, u8p]),
         "te_hash_pair": (i, [u8p, u8p, u8p]),

@@ -423,6 +423,28 @@ def recover_batch(slicer: Slicer, slices, objs: list[tuple[int, int, int, int, i
     _check(r, "recover")
 
 
+def recover_multi_batch(slicer: Slicer, slices, objs: list[tuple[int, int, int, int, int]], metas: bytes, out,
+                        stream=None) -> None:
+    """te_recover_multi_batch_device: several lost slices of each object from one decode.  objs are
+    (slices_off, slice_len, avail_mask, lost_mask, out_off); the j-th set bit of lost_mask is rebuilt
+    at out + out_off + j*slice_len.  metas as for recover_batch."""
+    arr = (_lib.te_recover_multi_object * max(1, len(objs)))(*[_lib.te_recover_multi_object(*o) for o in objs])
+    cfg = slicer._cfg()
+    mb = (C.c_uint8 * max(1, len(metas))).from_buffer_copy(metas if metas else b"\0")
+    r = lib.te_recover_multi_batch_device(slicer.coder.handle, C.byref(cfg), C.c_void_p(slices.data_ptr()), arr, mb,
+                                          len(objs), C.c_void_p(out.data_ptr()), _stream_ptr(stream))
+    _check(r, "recover")
+
+
+def recover_multi_launch_stats(coder: ClayCoder) -> dict:
+    """te_clay_recover_multi_launch_stats: the handle's last multi-slice recover -- launches of the
+    multi-output kernel, the most passes a stripe took, its jobs and stored rows, stripes and split
+    stripes, and the objects sent to the single-slice, generic and multi-output paths."""
+    st = _lib.te_recover_multi_stats()
+    _check(lib.te_clay_recover_multi_launch_stats(coder.handle, C.byref(st)), "recover")
+    return {f: int(getattr(st, f)) for f, _ in st._fields_}
+
+
 def _leaf_bytes(leaves, nobj: int, n: int):
     """nobj * n * 32 bytes of leaves (bytes, or a list per object of n 32-byte hashes) as a ctypes array."""
     b = bytes(leaves) if isinstance(leaves, (bytes, bytearray, memoryview)) else \

@@ -32,6 +32,7 @@
 #include "win_plan.hpp"
 #include "dec_class.hpp"
 #include "dec_plan.hpp"
+#include "rec_multi_plan.hpp"
 
 using namespace tec;
 
@@ -568,6 +569,12 @@ struct te_clay {
     te_snapshot_stats sns{};
     // the last data-verify call (te_verify_data_batch_device / _host, te_slicer_verify_data)
     te_verify_data_stats vds{};
+    // te_recover_multi_batch_device: the sub-masks of a (padded erasure mask, lost nodes) pair
+    // (rec_multi_split) and the compiled program of each (rec_multi_key), host work done once per
+    // handle; the programs live in `dstore` beside the decode's; the last call's stats
+    std::unordered_map<uint64_t, std::vector<uint64_t>> rm_split;
+    std::unordered_map<uint64_t, DecCache> rm_cache;
+    te_recover_multi_stats rms{};
 };
 
 // Drain and free everything a handle holds on its device (on that device).
@@ -812,6 +819,13 @@ int te_clay_verify_data_launch_stats(te_clay *c, te_verify_data_stats *out) {
     if (!c || !out) return TE_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     *out = c->vds;
+    return TE_OK;
+}
+
+int te_clay_recover_multi_launch_stats(te_clay *c, te_recover_multi_stats *out) {
+    if (!c || !out) return TE_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    *out = c->rms;
     return TE_OK;
 }
 
@@ -3790,7 +3804,330 @@ static int percall_decode_device(te_clay *c, const te_slicer_cfg *cfg, const Dec
     TE_HIP(hipStreamSynchronize(c->stream));
     return TE_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// Multi-output rebuild (te_recover_multi_batch_device, recover.rs:411-442 for several slices of
+// one object): rec_multi_plan.hpp has the rules, recover_multi.hip the kernel
+// ------------------------------------------------------------------------------------------
+namespace {
+struct RecMultiItem {
+    DecItem it;        // validated like Slicer::decode; in_base set
+    uint32_t lost;     // the lost slices
+    uint64_t out_off;  // the j-th of them at d_out + out_off + j * it.slice_len
+    uint64_t cs, ns;   // the slices' chunk size and stripes (an empty blob: one zero chunk)
+    uint64_t chunk_index, meta_w[6];
+};
+
+// One object's checks, host only: the masks, then Slicer::decode's, then the slice length
+int rec_multi_validate(const te_clay *c, const te_recover_multi_object &o, const uint8_t *meta48, RecMultiItem &m) {
+    int r = rec_multi_check(c->h.n, c->h.k, o.avail_mask, o.lost_mask);
+    if (r || (r = decode_validate(c, meta48, o.slice_len, o.avail_mask, m.it))) return r;
+    te_slice_metadata md;
+    te_slice_metadata_from_slice(meta48, TE_META_SIZE, &md);
+    te_geometry g;
+    te_slicer_geometry(c, m.it.blob_len, &g);
+    if (g.slice_len != o.slice_len) return TE_ERR_INVALID_LAYOUT;
+    m.it.in_base = o.slices_off;
+    m.lost = o.lost_mask;
+    m.out_off = o.out_off;
+    m.cs = g.chunk_size;
+    m.ns = g.num_stripes;
+    m.chunk_index = md.chunk_index;
+    for (int w = 0; w < 6; w++) m.meta_w[w] = get_u64(meta48 + 8 * w);
+    return TE_OK;
+}
+
+// The sub-masks of a stripe's (padded erasure mask, lost nodes) and their programs, compiled once
+// per handle (caller holds c->mu).  Empty: no program (the caller takes the generic path).
+const std::vector<uint64_t> *rec_multi_subs(te_clay *c, uint64_t emask, uint64_t lostn) {
+    const uint64_t key = rec_multi_key(emask, lostn);
+    auto f = c->rm_split.find(key);
+    if (f != c->rm_split.end()) return &f->second;
+    te_clay::DecCache base;
+    if (!c->h.gpe_pattern(emask, base.P, base.planes)) return nullptr;
+    base.P.planes_off = 0;
+    std::vector<RecMultiProg> progs;
+    std::vector<uint64_t> subs = rec_multi_split(c->h, base.P, lostn, &progs);
+    for (size_t i = 0; i < subs.size(); i++) {
+        const uint64_t k = rec_multi_key(emask, subs[i]);
+        if (c->rm_cache.count(k)) continue;
+        te_clay::DecCache d = base;
+        d.staged = progs[i].steps.size() == te_clay::DecStore::kSteps;
+        if (!d.staged) return nullptr;
+        d.H = progs[i].H;
+        d.steps = std::move(progs[i].steps);
+        d.orient = progs[i].orient;
+        c->rm_cache.emplace(k, std::move(d));
+    }
+    return &c->rm_split.emplace(key, std::move(subs)).first->second;
+}
+
+// The objects on the multi-output kernel: a job per (stripe, sub-mask), all of one chunk size and
+// slice length in one launch -- a split stripe's passes are jobs of the same launch, reading the
+// same resident slices.  The programs go through the decode's device store and descriptor arena
+// (dec_image / dec_upload).  TE_ERR_UNSUPPORTED, before anything is enqueued: a stripe without a
+// program.  Caller holds c->mu, the handle's device current.
+int recover_multi_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const std::vector<RecMultiItem> &items,
+                          uint8_t *d_out, hipStream_t s, te_recover_multi_stats &st_out) {
+    const ClayHost &h = c->h;
+    if (c->rm_cache.size() > c->dstore.max_cap) {
+        c->rm_cache.clear();
+        c->rm_split.clear();
+    }
+    DecCall D{c, s, cfg->rotated};
+    std::unordered_map<uint64_t, uint32_t> pat_index;
+    std::map<DecGroupKey, std::vector<RmSlots>> tabs;
+    te_recover_multi_stats add{};
+    for (const RecMultiItem &m : items) {
+        const DecItem &it = m.it;
+        const uint64_t nlost = (uint64_t)__builtin_popcount(m.lost);
+        const DecGroupKey gk{it.cs, it.slice_len};
+        for (uint64_t st = 0; st < it.ns; st++) {
+            const uint64_t emask = stripe_emask(h, D.rotated, it.avail, st);
+            const uint64_t lostn = rec_multi_lost_nodes(h, D.rotated, m.lost, st);
+            const std::vector<uint64_t> *subs = rec_multi_subs(c, emask, lostn);
+            if (!subs || subs->empty()) return TE_ERR_UNSUPPORTED;
+            for (uint64_t sub : *subs) {
+                const uint64_t key = rec_multi_key(emask, sub);
+                const auto f = pat_index.emplace(key, (uint32_t)D.plan.keys.size());
+                if (f.second) {
+                    D.plan.keys.push_back(key);
+                    D.cached.push_back(&c->rm_cache.at(key));
+                }
+                GpeJob g{};
+                g.in = d_slices + it.in_base + st * it.cs;
+                g.in_len = ~0ull;
+                g.out = d_out + m.out_off + st * it.cs;  // slot j's chunk of this stripe at + j * slice_len
+                g.out_len = (nlost - 1) * it.slice_len + it.cs;
+                g.rot = D.rotated ? (uint32_t)((st * TE_ROTATION_STEP) % (uint64_t)h.n) : 0u;
+                g.pattern = f.first->second;
+                D.plan.groups[gk].push_back(g);
+                tabs[gk].push_back(rec_multi_slots(h, D.rotated, m.lost, sub, st));
+                add.jobs++;
+                add.out_rows += (uint64_t)__builtin_popcountll(sub) * (uint64_t)h.alpha;
+            }
+            add.stripes++;
+            add.split_stripes += subs->size() > 1;
+            add.passes = std::max(add.passes, (uint32_t)subs->size());
+        }
+    }
+    if (D.plan.groups.empty()) return TE_OK;
+    for (const te_clay::DecCache *dc : D.cached) {
+        D.lds_rows = std::max(D.lds_rows, recover_multi_rows(dc->H.nslots));
+        D.nscr_max = std::max(D.nscr_max, dc->H.nscratch);
+        D.max_er = std::max(D.max_er, dc->P.nerased);
+    }
+    D.small_dec = add.jobs <= kDecSmallStripes;  // a per-call rebuild: one wave per workgroup
+    int r = dec_image(D);
+    if (r) return r;
+    Arena &A = c->dec;
+    std::vector<size_t> tab_off;
+    for (auto &o : D.offs) tab_off.push_back(A.put(tabs.at(o.first).data(), tabs.at(o.first).size() * sizeof(RmSlots)));
+    if ((r = dec_upload(D))) return r;
+    size_t scratch_bytes = 0;
+    for (auto &o : D.offs) scratch_bytes = std::max(scratch_bytes, recover_multi_scratch_bytes(dec_table_args(D, o)));
+    if ((r = A.workspace(scratch_bytes, s, &D.scratch))) return r;
+    KTimer kt(s);
+    for (size_t i = 0; i < D.offs.size(); i++) {
+        DecArgs a = dec_table_args(D, D.offs[i]);
+        a.scratch = D.scratch;
+        a.out_stride = D.offs[i].first.slice_len;  // between output slots
+        TE_HIP(launch_recover_multi(a, A.at<RmSlots>(tab_off[i]), s));
+        add.multi_launches++;
+    }
+    kt.stop();
+    if (D.in_store) TE_HIP(c->dstore.readers.record(s));
+    if ((r = A.mark_done(s))) return r;
+    st_out.multi_launches += add.multi_launches;
+    st_out.passes = std::max(st_out.passes, add.passes);
+    st_out.jobs += add.jobs;
+    st_out.out_rows += add.out_rows;
+    st_out.stripes += add.stripes;
+    st_out.split_stripes += add.split_stripes;
+    return TE_OK;
+}
+
+// The generic path: the existing decode into the object, the existing encode of all n slices, the
+// lost ones kept -- in windows of bounded workspace, as recover_batch's.  Caller holds c->mu.
+int recover_multi_generic(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, std::vector<RecMultiItem> &items,
+                          uint8_t *d_out, hipStream_t s) {
+    const uint64_t n = (uint64_t)c->h.n;
+    constexpr uint64_t kWinBlob = 1ull << 30, kWinSlices = 3ull << 30;
+    struct Win { size_t b, e; uint64_t blob, slices; };
+    std::vector<Win> wins;
+    uint64_t max_blob = 16, max_slices = 16;
+    for (size_t i = 0; i < items.size();) {
+        Win w{i, i, 0, 0};
+        while (w.e < items.size()) {
+            const uint64_t bb = align16(items[w.e].it.blob_len), sb = n * items[w.e].it.slice_len;
+            if (w.e > w.b && (w.blob + bb > kWinBlob || w.slices + sb > kWinSlices)) break;
+            w.blob += bb;
+            w.slices += sb;
+            w.e++;
+        }
+        max_blob = std::max(max_blob, w.blob + 16);
+        max_slices = std::max(max_slices, w.slices + 16);
+        wins.push_back(w);
+        i = w.e;
+    }
+    if (max_blob > c->rec_blob.cap || max_slices > c->rec_slices.cap) {
+        if (c->rec_pending) TE_HIP(hipEventSynchronize(c->rec_done));  // queued work may still use them
+    } else if (c->rec_pending && c->rec_stream != s) {
+        TE_HIP(hipStreamWaitEvent(s, c->rec_done, 0));
+    }
+    TE_HIP(c->rec_blob.ensure(max_blob));
+    TE_HIP(c->rec_slices.ensure(max_slices));
+    uint8_t *const blob = c->rec_blob.as<uint8_t>(), *const slices = c->rec_slices.as<uint8_t>();
+    int r = TE_OK;
+    for (const Win &w : wins) {
+        std::vector<DecItem> dit;
+        std::vector<te_object> wenc;
+        uint64_t bo = 0, so = 0;
+        for (size_t i = w.b; i < w.e; i++) {
+            DecItem it = items[i].it;
+            it.out_off = bo;
+            dit.push_back(it);
+            wenc.push_back(te_object{bo, it.blob_len, so, items[i].chunk_index});
+            bo += align16(it.blob_len);
+            so += n * it.slice_len;
+        }
+        if ((r = decode_enqueue(c, cfg, d_slices, dit.data(), dit.size(), blob, s, false))) break;
+        if ((r = encode_enqueue(c, cfg, blob, wenc.data(), wenc.size(), slices, s, false))) break;
+        std::vector<CopyJob> jobs;
+        std::vector<MetaJob> metas;
+        for (size_t i = w.b; i < w.e; i++) {
+            const RecMultiItem &m = items[i];
+            const uint64_t slen = m.it.slice_len, body = m.ns * m.cs;
+            uint64_t j = 0;
+            for (uint32_t sl = 0; sl < (uint32_t)n; sl++) {
+                if (!((m.lost >> sl) & 1u)) continue;
+                uint8_t *dst = d_out + m.out_off + j++ * slen;
+                jobs.push_back(CopyJob{slices + wenc[i - w.b].out_off + (uint64_t)sl * slen, dst, body, body});
+                MetaJob mj{};
+                mj.dst = dst + body;
+                for (int k = 0; k < 6; k++) mj.words[k] = m.meta_w[k];
+                metas.push_back(mj);
+            }
+        }
+        if ((r = gather_meta_enqueue(c->rec, s, jobs, metas))) break;
+    }
+    const int r2 = rec_mark_done(c, s);
+    return r ? r : r2;
+}
+
+// locked = the caller holds the handle's lock (te_slicer_recover_multi)
+int recover_multi_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_multi_object *objs,
+                        const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool locked) {
+    if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
+    const ClayHost &h = c->h;
+    std::vector<RecMultiItem> multi, generic;
+    std::vector<te_recover_object> single;  // one per lost slice of a single-path object
+    std::vector<uint8_t> single_meta;
+    te_recover_multi_stats st{};
+    for (size_t i = 0; i < nobj; i++) {
+        RecMultiItem m{};
+        const uint8_t *meta = h_meta + i * TE_META_SIZE;
+        if (int r = rec_multi_validate(c, objs[i], meta, m)) return r;
+        switch (rec_multi_route(h, (uint32_t)__builtin_popcount(m.lost), m.it.ns, m.it.cs, m.it.slice_len)) {
+            case kRecMultiKernel: multi.push_back(m); break;
+            case kRecMultiGeneric: generic.push_back(m); break;
+            default: {
+                uint64_t j = 0;
+                for (uint32_t sl = 0; sl < (uint32_t)h.n; sl++) {
+                    if (!((m.lost >> sl) & 1u)) continue;
+                    single.push_back(te_recover_object{objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask, sl,
+                                                       objs[i].out_off + j++ * objs[i].slice_len});
+                    single_meta.insert(single_meta.end(), meta, meta + TE_META_SIZE);
+                }
+                st.single_objects++;
+            }
+        }
+    }
+    if (nobj == 0) return TE_OK;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
+    if (!locked) lk.lock();
+    c->dls = te_decode_launch_stats{};
+    c->els = te_encode_launch_stats{};
+    c->rms = te_recover_multi_stats{};
+    if (!single.empty()) {  // the single-slice path, as it is: it takes the lock itself
+        if (!locked) lk.unlock();
+        const int r = recover_batch(c, cfg, d_slices, single.data(), single_meta.data(), single.size(), d_out, stream, true, locked);
+        if (r) return r;
+        if (!locked) lk.lock();
+    }
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    hipStream_t s = (hipStream_t)stream;
+    if (!multi.empty()) {
+        const int r = recover_multi_enqueue(c, cfg, d_slices, multi, d_out, s, st);
+        if (r == TE_ERR_UNSUPPORTED) {
+            generic.insert(generic.end(), multi.begin(), multi.end());
+            multi.clear();
+        } else if (r) {
+            return r;
+        }
+        std::vector<MetaJob> metas;
+        for (const RecMultiItem &m : multi)
+            for (uint64_t j = 0; j < (uint64_t)__builtin_popcount(m.lost); j++) {
+                MetaJob mj{};
+                mj.dst = d_out + m.out_off + j * m.it.slice_len + m.ns * m.cs;
+                for (int k = 0; k < 6; k++) mj.words[k] = m.meta_w[k];
+                metas.push_back(mj);
+            }
+        if (!metas.empty()) {
+            if (c->rec_pending && c->rec_stream != s) TE_HIP(hipStreamWaitEvent(s, c->rec_done, 0));
+            const int rm = gather_meta_enqueue(c->rec, s, {}, metas), r2 = rec_mark_done(c, s);
+            if (rm || r2) return rm ? rm : r2;
+        }
+    }
+    st.multi_objects = multi.size();
+    st.generic_objects = generic.size();
+    if (!generic.empty())
+        if (int r = recover_multi_generic(c, cfg, d_slices, generic, d_out, s)) return r;
+    c->rms = st;
+    return TE_OK;
+}
+}  // namespace
 extern "C" {
+
+int te_recover_multi_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                  const te_recover_multi_object *objs, const uint8_t *h_meta, size_t nobj, uint8_t *d_out,
+                                  void *stream) {
+    return recover_multi_batch(c, cfg, d_slices, objs, h_meta, nobj, d_out, stream, false);
+}
+
+// Per call: the present slices go up once (upload_slices, the decode's staging), every lost slice
+// comes back from the one device buffer
+int te_slicer_recover_multi(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *const *slices, size_t slice_len,
+                            uint32_t lost_mask, uint8_t *const *out) {
+    if (!c || !cfg || !slices || !out) return TE_ERR_INVALID_ARG;
+    const ClayHost &h = c->h;
+    int first;
+    const uint32_t avail = slices_avail(slices, h.n, &first);
+    int r = rec_multi_check(h.n, h.k, avail, lost_mask);
+    if (r) return r;
+    const size_t nlost = (size_t)__builtin_popcount(lost_mask);
+    for (size_t j = 0; j < nlost; j++)
+        if (!out[j]) return TE_ERR_INVALID_ARG;
+    if (first < 0) return TE_ERR_NOT_ENOUGH_SLICES;
+    if (slice_len < TE_META_SIZE) return TE_ERR_INVALID_LAYOUT;
+    const uint8_t *meta = slices[first] + slice_len - TE_META_SIZE;
+    const te_recover_multi_object o{0, slice_len, avail, lost_mask, 0};
+    RecMultiItem m{};
+    if ((r = rec_multi_validate(c, o, meta, m))) return r;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    if ((r = ensure_stream(c))) return r;
+    if ((r = upload_slices(c, slices, slice_len, nlost * slice_len))) return r;
+    if ((r = recover_multi_batch(c, cfg, c->io_in.as<uint8_t>(), &o, meta, 1, c->io_out.as<uint8_t>(), c->stream, true))) return r;
+    for (size_t j = 0; j < nlost; j++)
+        TE_HIP(hipMemcpyAsync(out[j], c->io_out.as<uint8_t>() + j * slice_len, slice_len, hipMemcpyDeviceToHost, c->stream));
+    TE_HIP(hipStreamSynchronize(c->stream));
+    return TE_OK;
+}
 
 int te_clay_decode(te_clay *c, const uint8_t *const *chunks, size_t cs, uint8_t *out, size_t cap) {
     if (!c || !chunks || !out) return TE_ERR_INVALID_ARG;

@@ -268,6 +268,26 @@ uint32_t decode_stage_rows(uint32_t nslots, uint32_t max_out);  // LDS rows of a
 bool decode_stage_fits(uint32_t nslots, uint32_t max_out);
 uint32_t decode_stage_g(uint32_t words_per_stripe, uint32_t gmax = 0);  // waves per workgroup
 
+// Multi-output rebuild kernel (recover_multi.hip): the table-driven decode's program with the
+// stripe's lost nodes as outputs (dec_prog's out_mask), each output row stored to the slice that
+// holds its node.  RmSlots is job j's table: internal node -> output slot (slot s is the slice at
+// GpeJob::out + s * DecArgs::out_stride), kRmNoSlot for a node this job does not store.
+constexpr uint32_t kRmNoSlot = 0xffu;
+constexpr uint32_t kRmMaxLdsRows = 64;  // zero + trash + slots (g = 2: 32 KB), decode_stage.hip's budget
+struct RmSlots {
+    uint8_t slot[32];
+};
+// LDS rows of a program, and whether the kernel takes it: no staging rows (direct output), so the
+// same count as decode_stage_rows / decode_stage_fits of a direct-output build, and at most
+// kDecMaxOut flush items per step (the packed step form)
+inline uint32_t recover_multi_rows(uint32_t nslots) { return 2 + nslots; }
+inline bool recover_multi_fits(uint32_t nslots, uint32_t max_out) {
+    return max_out <= (uint32_t)kDecMaxOut && recover_multi_rows(nslots) <= kRmMaxLdsRows;
+}
+uint32_t recover_multi_g(uint32_t words_per_stripe, uint32_t gmax = 0);  // waves per workgroup
+size_t recover_multi_scratch_bytes(const DecArgs &a);
+hipError_t launch_recover_multi(DecArgs a, const RmSlots *slots, hipStream_t s);
+
 // Per-pattern decode kernels compiled at run time (dec_rtc.cpp, dec_fixed.hpp), per handle.
 using dfix_args = dfix::Args;
 static_assert(sizeof(dfix::Job) == sizeof(GpeJob) && offsetof(dfix::Job, rot) == offsetof(GpeJob, rot), "dfix::Job");

@@ -636,6 +636,32 @@ class Slicer:
         _check(r, "decode")
         return bytes(out)[:got.value]
 
+    def recover_many(self, slices: list[tuple[int, bytes]], lost: list[int]) -> dict[int, bytes]:
+        """te_slicer_recover_multi: `reconstruct` (recover.rs:411-442) for several lost slices of one
+        object -- the peers' slices go to the device once, every slice index in `lost` comes back."""
+        if not slices:
+            raise DecodeError("NotEnoughSlices")
+        n = self.n()
+        slice_len = len(slices[0][1])
+        ptrs = (C.c_void_p * n)()
+        keep = []
+        for idx, data in slices:
+            if not (0 <= idx < n) or len(data) != slice_len or ptrs[idx]:
+                raise DecodeError("InvalidLayout")
+            b = _buf(data)
+            keep.append(b)
+            ptrs[idx] = C.cast(b, C.c_void_p)
+        want = sorted(set(lost))
+        if not want or len(want) != len(lost) or not all(0 <= i < n for i in want):
+            raise ValueError("lost: distinct slice indices below n")
+        outs = [(C.c_uint8 * max(1, slice_len))() for _ in want]
+        optrs = (C.c_void_p * len(want))(*[C.cast(o, C.c_void_p) for o in outs])
+        cfg = self._cfg()
+        r = lib.te_slicer_recover_multi(self.coder.handle, C.byref(cfg), ptrs, slice_len,
+                                        sum(1 << i for i in want), optrs)
+        _check(r, "recover")
+        return {i: bytes(o)[:slice_len] for i, o in zip(want, outs)}
+
     def decode_range(self, chunks: list[tuple[int, bytes]], start: int, length: int) -> bytes:
         """te_slicer_decode_range: Slicer::decode followed by bytes[start..start + length] (the
         gateway's object_response_ranged, routes.rs:90-91), touching only the window's stripes."""

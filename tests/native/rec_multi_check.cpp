@@ -1,0 +1,292 @@
+// Host check of the multi-output rebuild's host side (tape_amd/csrc/rec_multi_plan.hpp), built and
+// run by tests/test_rec_multi_host.py.
+//   values  a fixed-seed sample of (survivor set, lost subset) pairs of Clay(20,7,16) -- every
+//           a0 = 0..7 known column-0 nodes, lost sets of 2, 3, 7 and 13 slices, in either column
+//           and across both, identity and rotated layouts at several stripe indices: the split
+//           rule's sub-masks, each one's program (ClayHost::dec_prog with the sub-mask as out_mask)
+//           interpreted byte by byte with the pattern's own matrix tables, every output row sent
+//           through the job's node -> slot table, must rebuild every lost slice's chunk of a
+//           stripe encoded by the oracle (oracle/clay_oracle.c), and store nothing else.
+//   split   for one survivor set per a0 and every lost-set size 1..13: the sub-masks partition
+//           the lost nodes, each compiles and fits (recover_multi_fits = decode_stage_fits of the
+//           direct-output kernel, and kDecMaxOut items a step), a set that fits whole is one part.
+//   args    rec_multi_check and rec_multi_route at their edges.
+// Exit status = number of failed checks.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+#include <vector>
+#include "rec_multi_plan.hpp"
+
+extern "C" {
+int oc_clay_sizeof(void);
+int oc_clay_init(void *c, int n, int k, int d);
+size_t oc_chunk_size_for(const void *c, size_t input_len);
+int oc_clay_encode(const void *c, const uint8_t *data, size_t len, uint8_t *out);
+}
+
+using namespace tec;
+
+static int bad = 0;
+#define CHECK(x)                                                   \
+    do {                                                           \
+        if (!(x)) {                                                \
+            if (bad++ < 20) printf("line %d: %s\n", __LINE__, #x); \
+        }                                                          \
+    } while (0)
+
+static constexpr int N = 20, K = 7;
+static ClayHost H;
+
+static uint8_t mul4(const uint32_t t[4], uint8_t x) {  // PermTab4 product, one byte
+    uint8_t r = 0;
+    for (int f = 0; f < 4; f++) r ^= (uint8_t)(t[f] >> (8 * ((x >> (2 * f)) & 3)));
+    return r;
+}
+static uint8_t pft3(uint8_t a, uint8_t b) { return (uint8_t)(a ^ gf_mul(2, (uint8_t)(a ^ b))); }
+
+// Interpret one program (decode_stage.hip's step semantics) over the stripe's chunks (by node),
+// every output row through `tab` into out (slot-major: slot s at out + s * cs).  rows: rows stored.
+static void run(const GpePattern &P, const std::vector<DecStep> &steps, const uint8_t *chunks, size_t cs, size_t sc,
+                const RmSlots &tab, std::vector<uint8_t> &out, std::vector<int> &written, long &rows) {
+    const int NK = (int)P.nknown, NE = (int)P.nerased;
+    auto kidx = [&](int node) {
+        for (int j = 0; j < NK; j++)
+            if ((int)P.known[j] == node) return j;
+        CHECK(!"partner is a known node");
+        return 0;
+    };
+    auto in = [&](int node, int z, size_t b) { return chunks[(size_t)node * cs + (size_t)z * sc + b]; };
+    uint8_t slot[512], scr[512];
+    bool slot_ok[512], scr_ok[512];
+    for (size_t b = 0; b < sc; b++) {
+        memset(slot_ok, 0, sizeof slot_ok);
+        memset(scr_ok, 0, sizeof scr_ok);
+        for (const DecStep &S : steps) {
+            const int z = (int)S.z;
+            auto put = [&](uint32_t loc, uint8_t v) {
+                if (loc == kLocNone) return;
+                const uint32_t ty = loc >> 24, ix = loc & 0xffffffu;
+                if (ty == kLocStage) {
+                    CHECK(ix < S.nout && S.nout <= (uint32_t)kDecMaxOut);
+                    const uint32_t it = S.out[ix], node = it & 0xffu, zz = it >> 8;
+                    CHECK(node < (uint32_t)N && zz < 100);
+                    const uint8_t s = tab.slot[node];
+                    if (s == kRmNoSlot) return;  // the kernel drops it
+                    out[(size_t)s * cs + zz * sc + b] = v;
+                    written[(size_t)s * cs + zz * sc + b]++;
+                    rows += b == 0;
+                } else {
+                    CHECK(ix < 512);
+                    (ty == kLocSlot ? slot : scr)[ix] = v;
+                    (ty == kLocSlot ? slot_ok : scr_ok)[ix] = true;
+                }
+            };
+            auto get = [&](uint32_t loc) {
+                const uint32_t ty = loc >> 24, ix = loc & 0xffffffu;
+                CHECK(ix < 512 && (ty == kLocSlot ? slot_ok : scr_ok)[ix]);
+                return (ty == kLocSlot ? slot : scr)[ix];
+            };
+            uint8_t u[kDecMaxK], v[kDecMaxE] = {};
+            for (int j = 0; j < NK; j++) {
+                const uint8_t o = in((int)P.known[j], z, b);
+                CHECK(S.kout[j] == kLocNone);  // a survivor is never an output
+                if (S.kk[j] == kKnRed) u[j] = o;
+                else if (S.kk[j] == kKnInput) u[j] = pft3(o, in((int)P.known[kidx((int)(S.kp[j] & 0xffu))], (int)(S.kp[j] >> 8), b));
+                else if (S.kk[j] == kKnLoc) u[j] = pft3(o, get(S.kp[j]));
+                else CHECK(!"known kind of the table kernel");
+            }
+            for (int e = 0; e < NE; e++)
+                if (S.ek[e] == kErFinish) v[e] = get(S.ep[e]);
+            for (int e = 0; e < NE; e++) {
+                if (S.ek[e] == kErSkip) continue;
+                uint8_t a = 0;
+                for (int j = 0; j < NK; j++) a ^= mul4(P.D4[e][j], u[j]);
+                switch (S.ek[e]) {
+                    case kErRed: put(S.ed0[e], a); break;
+                    case kErType1: {
+                        const uint8_t k = in((int)P.known[kidx((int)(S.ep[e] & 0xffu))], (int)(S.ep[e] >> 8), b);
+                        const uint8_t w = (uint8_t)(gf_mul(kPft.t_u[0], (uint8_t)(a ^ k)) ^ k);
+                        put(S.ed0[e], w);
+                        put(S.ed1[e], w);
+                        break;
+                    }
+                    case kErPark: put(S.ep[e], a); break;
+                    case kErFinish:
+                        put(S.ed0[e], pft3(a, v[e]));
+                        put(S.epd[e], pft3(v[e], a));
+                        break;
+                    default: CHECK(!"erased kind of the table kernel");
+                }
+            }
+        }
+    }
+}
+
+static uint32_t pick(std::mt19937_64 &rng, uint32_t from, int count) {  // `count` random bits of `from`
+    uint32_t m = 0;
+    while (__builtin_popcount(m) < count) {
+        const uint32_t b = 1u << (rng() % N);
+        if (from & b) m |= b;
+    }
+    return m;
+}
+// survivor shards with a0 of them in column 0
+static uint32_t survivors(std::mt19937_64 &rng, int a0) { return pick(rng, 0x3ffu, a0) | pick(rng, 0xffc00u, K - a0); }
+
+static void check_split(const GpePattern &P, uint64_t lost, const std::vector<uint64_t> &subs, long &nsplit) {
+    CHECK(!subs.empty());
+    uint64_t seen = 0;
+    for (uint64_t s : subs) {
+        CHECK(s != 0 && !(s & seen) && !(s & ~lost));
+        seen |= s;
+        RecMultiProg R;
+        CHECK(rec_multi_compile(H, P, s, R));
+        CHECK(recover_multi_fits(R.H.nslots, R.H.max_out) && R.H.max_out <= (uint32_t)kDecMaxOut);
+        CHECK(R.steps.size() == 102 && R.H.nsteps == 100);
+    }
+    CHECK(seen == lost);
+    RecMultiProg whole;
+    const bool fits = rec_multi_compile(H, P, lost, whole);
+    CHECK(fits == (subs.size() == 1));  // a set that fits whole is not split; a split one does not fit
+    nsplit += subs.size() > 1;
+}
+
+int main() {
+    if (H.init(N, K, 16) != 0) return 2;
+    std::vector<uint8_t> oc((size_t)oc_clay_sizeof());
+    oc_clay_init(oc.data(), N, K, 16);
+    const size_t len = 2800;  // sc = 2 bytes: chunk 200 B
+    const size_t cs = oc_chunk_size_for(oc.data(), len), sc = cs / 100;
+    std::vector<uint8_t> data(len), chunks(N * cs);
+    std::mt19937_64 rng(0x726d756c7469ull);
+    for (auto &x : data) x = (uint8_t)rng();
+    if (oc_clay_encode(oc.data(), data.data(), len, chunks.data()) != 0) return 2;
+    std::vector<uint16_t> pool;
+
+    // ---- values ----
+    long pairs = 0, passes = 0, nsplit = 0, rows_total = 0;
+    bool col_only[2] = {false, false}, col_both = false, rot_seen[2] = {false, false};
+    const int sizes[4] = {2, 3, 7, 13};
+    for (int a0 = 0; a0 <= 7; a0++)
+        for (int size : sizes)
+            for (int rep = 0; rep < 16; rep++) {
+                const int rotated = (int)(rng() % 2);
+                const uint64_t st = rng() % 23;
+                // the survivor shards of this stripe as slices, the lost slices among the rest
+                const uint32_t surv_sh = survivors(rng, a0);
+                uint32_t avail = 0;
+                for (uint32_t sh = 0; sh < (uint32_t)N; sh++)
+                    if ((surv_sh >> sh) & 1u) avail |= 1u << shard_to_slice(rotated, N, (uint32_t)st, sh);
+                const uint32_t all = (1u << N) - 1u;
+                uint32_t lost_sh = pick(rng, all & ~surv_sh, size);
+                // the small sizes also within one column each, where the erased nodes allow
+                if (size <= 3 && rep % 4 == 1 && __builtin_popcount(~surv_sh & 0x3ffu) >= size) lost_sh = pick(rng, ~surv_sh & 0x3ffu, size);
+                if (size <= 3 && rep % 4 == 2 && __builtin_popcount(~surv_sh & 0xffc00u) >= size) lost_sh = pick(rng, ~surv_sh & 0xffc00u, size);
+                uint32_t lost = 0;
+                for (uint32_t sh = 0; sh < (uint32_t)N; sh++)
+                    if ((lost_sh >> sh) & 1u) lost |= 1u << shard_to_slice(rotated, N, (uint32_t)st, sh);
+                CHECK(rec_multi_check(N, K, avail, lost) == TE_OK);
+                const uint64_t emask = stripe_emask(H, rotated, avail, st);
+                const uint64_t lostn = rec_multi_lost_nodes(H, rotated, lost, st);
+                CHECK(lostn == lost_sh && !(lostn & ~emask) && emask == (all & ~surv_sh));
+                col_only[0] = col_only[0] || !(lostn & 0xffc00u);
+                col_only[1] = col_only[1] || !(lostn & 0x3ffu);
+                col_both = col_both || ((lostn & 0x3ffu) && (lostn & 0xffc00u));
+                rot_seen[rotated] = true;
+                GpePattern P;
+                pool.clear();
+                if (!H.gpe_pattern(emask, P, pool)) return 2;
+                const std::vector<uint64_t> subs = rec_multi_split(H, P, lostn);
+                check_split(P, lostn, subs, nsplit);
+                // all 13 erased nodes never fit one pass (tests/test_gpu_recover_multi.py's split case relies on it)
+                CHECK(size != 13 || subs.size() >= 2);
+                std::vector<uint8_t> out((size_t)size * cs, 0xEE);
+                std::vector<int> written((size_t)size * cs, 0);
+                long rows = 0;
+                for (uint64_t sub : subs) {
+                    RecMultiProg R;
+                    std::vector<DecStep> raw;
+                    if (!rec_multi_compile(H, P, sub, R, &raw)) continue;  // counted by check_split
+                    const RmSlots tab = rec_multi_slots(H, rotated, lost, sub, st);
+                    for (int node = 0; node < 32; node++)
+                        CHECK((tab.slot[node] != kRmNoSlot) == (node < N && ((sub >> node) & 1ull)));
+                    run(P, raw, chunks.data(), cs, sc, tab, out, written, rows);
+                    passes++;
+                }
+                CHECK(rows == (long)size * 100);  // alpha rows per lost node, each once
+                uint32_t j = 0;
+                for (uint32_t sl = 0; sl < (uint32_t)N; sl++) {
+                    if (!((lost >> sl) & 1u)) continue;
+                    const uint32_t sh = slice_to_shard(rotated, N, (uint32_t)st, sl);
+                    const bool same = memcmp(out.data() + (size_t)j * cs, chunks.data() + (size_t)sh * cs, cs) == 0;
+                    if (!same) printf("FAIL a0 %d size %d avail %05x lost %05x rot %d st %d slot %u\n", a0, size, avail, lost, rotated, (int)st, j);
+                    CHECK(same);
+                    j++;
+                }
+                for (int w : written) CHECK(w == 1);
+                rows_total += rows;
+                pairs++;
+            }
+    CHECK(pairs >= 500 && col_only[0] && col_only[1] && col_both && rot_seen[0] && rot_seen[1]);
+    // the check can fail: a table that sends a node to another slot must not reproduce the slices
+    {
+        const uint64_t emask = 0xfffffull & ~0x0c07cull;
+        GpePattern P;
+        pool.clear();
+        if (!H.gpe_pattern(emask, P, pool)) return 2;
+        const uint64_t lostn = 0x3ull;
+        RecMultiProg R;
+        std::vector<DecStep> raw;
+        CHECK(rec_multi_compile(H, P, lostn, R, &raw));
+        RmSlots tab = rec_multi_slots(H, 0, 0x3u, lostn, 0);
+        std::swap(tab.slot[0], tab.slot[1]);
+        std::vector<uint8_t> out(2 * cs, 0xEE);
+        std::vector<int> written(2 * cs, 0);
+        long rows = 0;
+        run(P, raw, chunks.data(), cs, sc, tab, out, written, rows);
+        CHECK(memcmp(out.data(), chunks.data(), 2 * cs) != 0 && memcmp(out.data(), chunks.data() + cs, cs) == 0);
+    }
+
+    // ---- split rule: one survivor set per a0, every lost-set size ----
+    long split_sets = 0, split_found = 0, whole_found = 0;
+    for (int a0 = 0; a0 <= 7; a0++) {
+        const uint32_t surv = survivors(rng, a0), er = ((1u << N) - 1u) & ~surv;
+        GpePattern P;
+        pool.clear();
+        if (!H.gpe_pattern(er, P, pool)) return 2;
+        for (int size = 1; size <= 13; size++)
+            for (int rep = 0; rep < (size == 13 ? 1 : 24); rep++) {
+                const uint64_t lostn = pick(rng, er, size);
+                long ns = 0;
+                check_split(P, lostn, rec_multi_split(H, P, lostn), ns);
+                split_found += ns;
+                whole_found += !ns;
+                split_sets++;
+            }
+    }
+    CHECK(split_found > 0 && whole_found > 0);  // both outcomes are exercised
+
+    // ---- arguments and routing ----
+    CHECK(rec_multi_check(N, K, 0x7f, 0) == TE_ERR_INVALID_ARG);
+    CHECK(rec_multi_check(N, K, 0x7f, 1u << 20) == TE_ERR_INVALID_ARG);
+    CHECK(rec_multi_check(N, K, 0x7f, 0x40) == TE_ERR_INVALID_ARG);
+    CHECK(rec_multi_check(N, K, 0x7f, 0x80) == TE_OK);
+    CHECK(rec_multi_check(N, K, 0x7f, 0xfff80) == TE_OK);
+    CHECK(rec_multi_check(N, K, 0x3f, 0xfffc0) == TE_ERR_INVALID_ARG);  // 14 lost slices
+    CHECK(rec_multi_check(N, K, 0x3f, 0x80) == TE_OK);                  // too few survivors is the decode's check
+    CHECK(rec_multi_route(H, 1, 3, 3000, 9048) == kRecMultiSingle);
+    CHECK(rec_multi_route(H, kRecMultiMinLost, 3, 3000, 9048) == kRecMultiKernel);
+    CHECK(rec_multi_route(H, kRecMultiMinLost - 1, 3, 3000, 9048) == kRecMultiSingle);
+    CHECK(rec_multi_route(H, 13, 0, 0, 248) == kRecMultiSingle);        // an empty blob
+    CHECK(rec_multi_route(H, 2, 1, 700, 748) == kRecMultiGeneric);      // sub-chunks of 7 bytes
+    CHECK(rec_multi_route(H, 2, 1, 800, 848) == kRecMultiKernel);
+    ClayHost h2;
+    if (h2.init(14, 10, 13) != 0) return 2;
+    CHECK(rec_multi_route(h2, 2, 1, 25600, 25648) == kRecMultiGeneric);  // no plane programs
+
+    printf("rec_multi pairs %ld passes %ld split %ld rows %ld split_sets %ld (split %ld whole %ld) bad %d\n", pairs, passes,
+           nsplit, rows_total, split_sets, split_found, whole_found, bad);
+    return bad > 255 ? 255 : bad;
+}
