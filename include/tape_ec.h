@@ -757,6 +757,25 @@ int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const
                                      const te_recover_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
                                      size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, uint32_t *h_ok,
                                      int *h_status, void *hip_stream);
+/* Multi-slice node recover with both of its checks: the node that owns L spools of a group runs
+ * recover.rs:77-244 once per spool, checking the peers and the rebuilt slice each time
+ * (recover.rs:207-218) around `reconstruct` (recover.rs:411-442).  This is
+ * te_recover_verified_batch_device's contract widened to a lost mask: every slice of avail_mask is
+ * hashed against h_leaves (nobj * n * 32 bytes), h_rejected_mask[o] = avail & ~good, the survivors
+ * are chosen on the host from the verified slices (one wait).  An object with fewer than k verified
+ * slices gets h_status[o] = TE_ERR_NOT_ENOUGH_SLICES, nothing written to its output range and
+ * h_ok_mask[o] = 0.  Every other object rebuilds as te_recover_multi_batch_device does (the same
+ * routing), then one verify launch hashes all rebuilt slices of all objects: h_ok_mask[o] has the
+ * bit of each lost slice whose rebuilt bytes hash to leaves[slice]; the bytes are written either
+ * way.  lost_mask is what the caller asked for: a rejected peer does not become a lost slice.
+ * Argument errors: te_recover_multi_batch_device's, and TE_ERR_INVALID_ARG for an out_off,
+ * slices_off or slice_len that is no multiple of 4; all of them are returned before the call looks
+ * for a device.  Waits for the results (h_ok_mask is host memory). */
+int te_recover_multi_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                           const te_recover_multi_object *objs, const uint8_t *h_meta,
+                                           const uint8_t *h_leaves, size_t nobj, uint8_t *d_out,
+                                           uint32_t *h_rejected_mask, uint32_t *h_ok_mask, int *h_status,
+                                           void *hip_stream);
 /* Repair with its check (repair.rs:339-341): te_repair_batch_device, then verify_slice(plan.lost,
  * repaired) on the device into h_ok[o].  Helper fragments have no leaf of their own, so only the
  * result is checked.  h_leaves: nobj * n * 32 bytes.  The repaired bytes are written either way.
@@ -917,6 +936,32 @@ int te_repair_batch_host(te_clay *c, const uint8_t *h_helpers, const te_repair_o
 int te_recover_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_recover_object *objs,
                           const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *h_out,
                           uint32_t *h_rejected_mask, uint32_t *h_ok, int *h_status, size_t window_bytes);
+/* The windows of te_recover_multi_batch_host, in te_recover_window_plan's shape: a multi-slice
+ * recover object (recover.rs:77-244 for each of its lost slices, one `reconstruct`
+ * recover.rs:411-442, the checks of recover.rs:207-218) counts popcount(avail_mask) * slice_len in
+ * plus popcount(lost_mask) * slice_len out.  Host only. */
+int te_recover_multi_window_plan(const te_clay *c, const te_recover_multi_object *objs, size_t nobj,
+                                 size_t window_bytes, size_t *cuts, size_t cap, size_t *nwindows);
+/* A node's multi-spool escalation HOST -> HOST: the L lost slices of each object from one upload of
+ * its peers (recover.rs:77-244 L times over: peers checked and the rebuilt slice checked,
+ * recover.rs:207-218, around one `reconstruct`, recover.rs:411-442).  te_recover_batch_host's
+ * contract and pipeline with te_recover_multi_verified_batch_device's masks: h_rejected_mask[o] the
+ * peers that fail their leaf, h_status[o] = TE_ERR_NOT_ENOUGH_SLICES (output range untouched,
+ * h_ok_mask[o] = 0) below k verified slices, else h_ok_mask[o] the bits of the lost slices whose
+ * rebuilt bytes hash to their leaf.  The j-th set bit of lost_mask lands at
+ * h_out + out_off + j * slice_len.  h_leaves == NULL is the unverified form: the mask and status
+ * arrays may be NULL and fewer than k present slices is the call's error.  Every object is
+ * validated (te_recover_multi_batch_device's checks) before anything is enqueued and before the
+ * call looks for a device.  The windows of te_recover_multi_window_plan run over the handle's three
+ * pipeline streams; hashing follows te_set_commit_hashing per window (a window with a slice_len,
+ * slices_off or out_off that is no multiple of 4 hashes on the host) and the results are identical
+ * in every mode.  Pageable or pinned: asked once per buffer, as te_recover_batch_host.  Zeroes and
+ * fills te_clay_rebuild_launch_stats (windows, pieces, bytes) and te_clay_recover_multi_launch_stats
+ * (summed over the call's windows).  Synchronous. */
+int te_recover_multi_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices,
+                                const te_recover_multi_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                size_t nobj, uint8_t *h_out, uint32_t *h_rejected_mask, uint32_t *h_ok_mask,
+                                int *h_status, size_t window_bytes);
 /* The handle's last te_repair_batch_host / te_recover_batch_host call (repair.rs:94-226,
  * recover.rs:77-244), zeroed when the call has passed its argument checks.  The kernels of the
  * call, summed over its windows, stay in te_clay_repair_launch_stats / te_clay_decode_launch_stats. */

@@ -313,6 +313,8 @@ def _load() -> C.CDLL:
                                                 u8p, sz, vp, u32p, C.POINTER(i), vp]),
         "te_recover_verified_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_object), u8p,
                                                  u8p, sz, vp, u32p, u32p, C.POINTER(i), vp]),
+        "te_recover_multi_verified_batch_device": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_multi_object),
+                                                       u8p, u8p, sz, vp, u32p, u32p, C.POINTER(i), vp]),
         "te_repair_verified_batch_device": (i, [vp, vp, C.POINTER(te_repair_object), u8p, sz, vp, u32p, vp]),
         "te_slicer_decode_verified": (i, [vp, C.POINTER(te_slicer_cfg), pp, sz, u8p, u8p, sz, szp, u32p]),
         "te_decode_window_plan": (i, [vp, C.POINTER(te_decode_object), u8p, sz, sz, szp, sz, szp]),
@@ -330,6 +332,9 @@ def _load() -> C.CDLL:
         "te_repair_batch_host": (i, [vp, vp, C.POINTER(te_repair_object), u8p, sz, vp, u32p, sz]),
         "te_recover_batch_host": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_object), u8p, u8p, sz, vp,
                                       u32p, u32p, C.POINTER(i), sz]),
+        "te_recover_multi_window_plan": (i, [vp, C.POINTER(te_recover_multi_object), sz, sz, szp, sz, szp]),
+        "te_recover_multi_batch_host": (i, [vp, C.POINTER(te_slicer_cfg), vp, C.POINTER(te_recover_multi_object), u8p, u8p,
+                                            sz, vp, u32p, u32p, C.POINTER(i), sz]),
         "te_clay_rebuild_launch_stats": (i, [vp, C.POINTER(te_rebuild_launch_stats)]),
         "te_outer_chunk_bytes": (sz, [u32, sz]),
         "te_outer_encode": (i, [u32, u32, u8p, sz, u8p, sz, szp]),

@@ -494,6 +494,33 @@ def recover_verified_batch(slicer: Slicer, slices, objs: list[tuple[int, int, in
     return [int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]], [int(x) for x in ok[:nobj]]
 
 
+def recover_multi_descs(objs: list[tuple[int, int, int, int, int]]):
+    """Prepared te_recover_multi_object array: (slices_off, slice_len, avail_mask, lost_mask, out_off) each."""
+    return (_lib.te_recover_multi_object * max(1, len(objs)))(*[_lib.te_recover_multi_object(*o) for o in objs])
+
+
+def recover_multi_verified_batch(slicer: Slicer, slices, objs: list[tuple[int, int, int, int, int]], metas: bytes,
+                                 leaves, out, stream=None):
+    """te_recover_multi_verified_batch_device: recover_multi_batch with both checks of
+    recover.rs:207-218 -- the peers verified before the rebuild, every rebuilt slice against its leaf
+    after.  objs as for recover_multi_batch.  Returns (status, rejected, ok_mask) per object: ok_mask
+    has the bit of each lost slice whose rebuilt bytes match (0 for an object that was not rebuilt);
+    the bytes are written either way.  Waits for the results."""
+    nobj = len(objs)
+    arr = objs if _is_desc(objs) else recover_multi_descs(objs)
+    cfg = slicer._cfg()
+    mb = (C.c_uint8 * max(1, len(metas))).from_buffer_copy(metas if metas else b"\0")
+    lb = _leaf_bytes(leaves, nobj, slicer.coder.n())
+    rej = (C.c_uint32 * max(1, nobj))()
+    ok = (C.c_uint32 * max(1, nobj))()
+    st = (C.c_int * max(1, nobj))()
+    r = lib.te_recover_multi_verified_batch_device(slicer.coder.handle, C.byref(cfg), C.c_void_p(slices.data_ptr()), arr,
+                                                   mb, lb, nobj, C.c_void_p(out.data_ptr()), rej, ok, st,
+                                                   _stream_ptr(stream))
+    _check(r, "recover")
+    return [int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]], [int(x) for x in ok[:nobj]]
+
+
 def reconstruct(slicer: Slicer, lost: int, peer_slices: list[tuple[int, bytes]]) -> bytes:
     """recover.rs:411-442 `reconstruct`: decode the peers' slices, re-encode, return slice `lost`
     (one object, host bytes in and out, through recover_batch)."""
@@ -617,6 +644,37 @@ def recover_host(slicer: Slicer, slices, objs, metas: bytes, out, leaves=None, w
     st = (C.c_int * max(1, nobj))() if verified else None
     r = lib.te_recover_batch_host(slicer.coder.handle, C.byref(cfg), C.c_void_p(_host_ptr(slices)), arr,
                                   _meta_bytes(metas), lb, nobj, C.c_void_p(_host_ptr(out)), rej, ok, st, window_bytes)
+    _check(r, "recover")
+    if not verified:
+        return None
+    return [int(x) for x in st[:nobj]], [int(x) for x in rej[:nobj]], [int(x) for x in ok[:nobj]]
+
+
+def recover_multi_window_plan(coder: ClayCoder, objs, window_bytes: int = 0) -> list[int]:
+    """te_recover_multi_window_plan: the cuts of recover_multi_batch_host's windows; host only.  objs
+    as for recover_multi_batch: an object counts its present and its lost slices, a slice length each."""
+    nobj = len(objs)
+    arr = objs if _is_desc(objs) else recover_multi_descs(objs)
+    return _window_plan(lib.te_recover_multi_window_plan, coder, arr, nobj, window_bytes, "recover")
+
+
+def recover_multi_batch_host(slicer: Slicer, slices, objs, metas: bytes, out, leaves=None, window_bytes: int = 0):
+    """te_recover_multi_batch_host: a node's multi-spool escalation (recover.rs:77-244 for every lost
+    slice of an object, from one upload of its peers) host -> host, pipelined in windows.  objs /
+    metas as for recover_multi_batch with offsets into the host buffers slices/out; only the slices
+    named in each avail_mask are read.  With leaves returns (status, rejected, ok_mask) per object as
+    recover_multi_verified_batch does, else None.  Synchronous."""
+    nobj = len(objs)
+    arr = objs if _is_desc(objs) else recover_multi_descs(objs)
+    cfg = slicer._cfg()
+    verified = leaves is not None
+    lb = _leaf_bytes(leaves, nobj, slicer.coder.n()) if verified else None
+    rej = (C.c_uint32 * max(1, nobj))() if verified else None
+    ok = (C.c_uint32 * max(1, nobj))() if verified else None
+    st = (C.c_int * max(1, nobj))() if verified else None
+    r = lib.te_recover_multi_batch_host(slicer.coder.handle, C.byref(cfg), C.c_void_p(_host_ptr(slices)), arr,
+                                        _meta_bytes(metas), lb, nobj, C.c_void_p(_host_ptr(out)), rej, ok, st,
+                                        window_bytes)
     _check(r, "recover")
     if not verified:
         return None

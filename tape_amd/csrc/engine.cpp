@@ -13,6 +13,7 @@
 #include <deque>
 #include <map>
 #include <unordered_map>
+#include <unordered_set>
 #include <mutex>
 #include <vector>
 #include <algorithm>
@@ -3818,6 +3819,19 @@ struct RecMultiItem {
     uint64_t chunk_index, meta_w[6];
 };
 
+// A window's figures into its call's (te_recover_multi_batch_host): sums, and the most passes
+void rec_multi_stats_add(te_recover_multi_stats &sum, const te_recover_multi_stats &w) {
+    sum.multi_launches += w.multi_launches;
+    sum.passes = std::max(sum.passes, w.passes);
+    sum.jobs += w.jobs;
+    sum.out_rows += w.out_rows;
+    sum.stripes += w.stripes;
+    sum.split_stripes += w.split_stripes;
+    sum.single_objects += w.single_objects;
+    sum.generic_objects += w.generic_objects;
+    sum.multi_objects += w.multi_objects;
+}
+
 // One object's checks, host only: the masks, then Slicer::decode's, then the slice length
 int rec_multi_validate(const te_clay *c, const te_recover_multi_object &o, const uint8_t *meta48, RecMultiItem &m) {
     int r = rec_multi_check(c->h.n, c->h.k, o.avail_mask, o.lost_mask);
@@ -3839,27 +3853,76 @@ int rec_multi_validate(const te_clay *c, const te_recover_multi_object &o, const
 
 // The sub-masks of a stripe's (padded erasure mask, lost nodes) and their programs, compiled once
 // per handle (caller holds c->mu).  Empty: no program (the caller takes the generic path).
-const std::vector<uint64_t> *rec_multi_subs(te_clay *c, uint64_t emask, uint64_t lostn) {
-    const uint64_t key = rec_multi_key(emask, lostn);
-    auto f = c->rm_split.find(key);
-    if (f != c->rm_split.end()) return &f->second;
+// The host work of one pair, pure ClayHost work (thread-safe): the split and each part's program.
+struct RecMultiPair {
+    bool ok = false;  // false: no pattern, or a part without a staged program
+    std::vector<uint64_t> subs;
+    std::vector<te_clay::DecCache> progs;  // one per sub-mask
+};
+void rec_multi_pair(const ClayHost &h, uint64_t emask, uint64_t lostn, RecMultiPair &R) {
     te_clay::DecCache base;
-    if (!c->h.gpe_pattern(emask, base.P, base.planes)) return nullptr;
+    if (!h.gpe_pattern(emask, base.P, base.planes)) return;
     base.P.planes_off = 0;
     std::vector<RecMultiProg> progs;
-    std::vector<uint64_t> subs = rec_multi_split(c->h, base.P, lostn, &progs);
-    for (size_t i = 0; i < subs.size(); i++) {
-        const uint64_t k = rec_multi_key(emask, subs[i]);
-        if (c->rm_cache.count(k)) continue;
+    R.subs = rec_multi_split(h, base.P, lostn, &progs);
+    for (size_t i = 0; i < R.subs.size(); i++) {
         te_clay::DecCache d = base;
         d.staged = progs[i].steps.size() == te_clay::DecStore::kSteps;
-        if (!d.staged) return nullptr;
+        if (!d.staged) return;
         d.H = progs[i].H;
         d.steps = std::move(progs[i].steps);
         d.orient = progs[i].orient;
-        c->rm_cache.emplace(k, std::move(d));
+        R.progs.push_back(std::move(d));
     }
-    return &c->rm_split.emplace(key, std::move(subs)).first->second;
+    R.ok = true;
+}
+// ... and its place in the handle's caches (caller holds c->mu)
+const std::vector<uint64_t> *rec_multi_commit(te_clay *c, uint64_t emask, uint64_t lostn, RecMultiPair &R) {
+    // a pair without programs is remembered as an empty split, which the caller reads as "take the
+    // generic path": it is not compiled again by a later call
+    if (!R.ok) return &c->rm_split.emplace(rec_multi_key(emask, lostn), std::vector<uint64_t>{}).first->second;
+    for (size_t i = 0; i < R.subs.size(); i++) {
+        const uint64_t k = rec_multi_key(emask, R.subs[i]);
+        if (!c->rm_cache.count(k)) c->rm_cache.emplace(k, std::move(R.progs[i]));
+    }
+    return &c->rm_split.emplace(rec_multi_key(emask, lostn), std::move(R.subs)).first->second;
+}
+const std::vector<uint64_t> *rec_multi_subs(te_clay *c, uint64_t emask, uint64_t lostn) {
+    auto f = c->rm_split.find(rec_multi_key(emask, lostn));
+    if (f != c->rm_split.end()) return &f->second;
+    RecMultiPair R;
+    rec_multi_pair(c->h, emask, lostn, R);
+    return rec_multi_commit(c, emask, lostn, R);
+}
+
+// The (padded erasure mask, lost nodes) pairs of a call that the handle has not seen, compiled
+// before the call enqueues, on up to 16 host threads as dec_precompile's patterns are (a first-time
+// pair is about a millisecond of host work: the split tries a program per part and orientation).
+// rec_multi_subs then finds every pair of the call in the cache.  Caller holds c->mu.
+void rec_multi_precompile(te_clay *c, int rotated, const std::vector<RecMultiItem> &items) {
+    const ClayHost &h = c->h;
+    std::vector<std::pair<uint64_t, uint64_t>> todo;
+    std::unordered_set<uint64_t> seen;
+    for (const RecMultiItem &m : items)
+        for (uint64_t st = 0; st < m.it.ns; st++) {
+            const uint64_t emask = stripe_emask(h, rotated, m.it.avail, st);
+            const uint64_t lostn = rec_multi_lost_nodes(h, rotated, m.lost, st);
+            const uint64_t key = rec_multi_key(emask, lostn);
+            if (!c->rm_split.count(key) && seen.insert(key).second) todo.push_back({emask, lostn});
+        }
+    if (todo.size() < 2) return;  // rec_multi_subs compiles the one inline
+    std::vector<RecMultiPair> out(todo.size());
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const size_t nth = std::min<size_t>({16, (size_t)hw, todo.size()});
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t i; (i = next.fetch_add(1)) < todo.size();) rec_multi_pair(h, todo[i].first, todo[i].second, out[i]);
+    };
+    std::vector<std::thread> th;
+    for (size_t t = 1; t < nth; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    for (size_t i = 0; i < todo.size(); i++) (void)rec_multi_commit(c, todo[i].first, todo[i].second, out[i]);
 }
 
 // The objects on the multi-output kernel: a job per (stripe, sub-mask), all of one chunk size and
@@ -3874,6 +3937,7 @@ int recover_multi_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d
         c->rm_cache.clear();
         c->rm_split.clear();
     }
+    rec_multi_precompile(c, cfg->rotated, items);
     DecCall D{c, s, cfg->rotated};
     std::unordered_map<uint64_t, uint32_t> pat_index;
     std::map<DecGroupKey, std::vector<RmSlots>> tabs;
@@ -4015,9 +4079,11 @@ int recover_multi_generic(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d
     return r ? r : r2;
 }
 
-// locked = the caller holds the handle's lock (te_slicer_recover_multi)
+// locked = the caller holds the handle's lock (te_slicer_recover_multi, the host rebuild pipeline)
+// part = a window of a host call, as recover_batch's: the decode / encode launch stats go on summing
+// (c->rms is this window's alone; the pipeline sums it)
 int recover_multi_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_multi_object *objs,
-                        const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool locked) {
+                        const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool locked, bool part = false) {
     if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
     const ClayHost &h = c->h;
     std::vector<RecMultiItem> multi, generic;
@@ -4047,8 +4113,10 @@ int recover_multi_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_s
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
     std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
     if (!locked) lk.lock();
-    c->dls = te_decode_launch_stats{};
-    c->els = te_encode_launch_stats{};
+    if (!part) {
+        c->dls = te_decode_launch_stats{};
+        c->els = te_encode_launch_stats{};
+    }
     c->rms = te_recover_multi_stats{};
     if (!single.empty()) {  // the single-slice path, as it is: it takes the lock itself
         if (!locked) lk.unlock();
@@ -5151,6 +5219,78 @@ int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const
     return TE_OK;
 }
 
+// te_recover_verified_batch_device widened to a lost mask: the same two verify launches and waits,
+// recover_multi_batch between them, and one verify item per rebuilt slice (its object's mask gets
+// the slice's bit).  Every argument check comes before the call looks for a device.
+int te_recover_multi_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                                           const te_recover_multi_object *objs, const uint8_t *h_meta,
+                                           const uint8_t *h_leaves, size_t nobj, uint8_t *d_out,
+                                           uint32_t *h_rejected_mask, uint32_t *h_ok_mask, int *h_status, void *stream) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_leaves || !h_status || !h_ok_mask) && nobj)) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    std::vector<int> pre(nobj, TE_OK);
+    for (size_t i = 0; i < nobj; i++) {
+        if (objs[i].slice_len % 4u || objs[i].slices_off % 4u || objs[i].out_off % 4u) return TE_ERR_INVALID_ARG;
+        RecMultiItem m{};
+        const int r = rec_multi_validate(c, objs[i], h_meta + i * TE_META_SIZE, m);
+        if (r && r != TE_ERR_NOT_ENOUGH_SLICES) return r;
+        pre[i] = r;
+    }
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    if (nobj == 0) return TE_OK;
+    std::vector<te_verify_item> vi;
+    for (size_t i = 0; i < nobj; i++) {
+        h_ok_mask[i] = 0;
+        verify_push_slices(vi, i, n, objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask & all);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<uint32_t> good(nobj);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        DeviceGuard dg(c->device);
+        TE_HIP(dg.err);
+        if (int r = verify_wait(c, d_slices, vi, h_leaves, nobj * n, nobj, good.data(), s)) return r;
+    }
+    // the objects with k verified peers, rebuilt from those; lost_mask stays what the caller asked for
+    std::vector<te_recover_multi_object> run;
+    std::vector<uint8_t> run_meta;
+    std::vector<size_t> run_of;
+    for (size_t i = 0; i < nobj; i++) {
+        uint32_t ok;
+        DecItem it{};
+        if (resolve_survivors(c, objs[i].avail_mask & all, objs[i].slice_len, h_meta + i * TE_META_SIZE, pre[i], good[i],
+                              h_rejected_mask ? h_rejected_mask + i : nullptr, h_status + i, ok, it))
+            continue;
+        te_recover_multi_object o = objs[i];
+        o.avail_mask = ok;
+        run.push_back(o);
+        run_meta.insert(run_meta.end(), h_meta + i * TE_META_SIZE, h_meta + (i + 1) * TE_META_SIZE);
+        run_of.push_back(i);
+    }
+    if (run.empty()) {
+        std::lock_guard<std::mutex> lk(c->mu);
+        c->rms = te_recover_multi_stats{};
+        return TE_OK;
+    }
+    int r = recover_multi_batch(c, cfg, d_slices, run.data(), run_meta.data(), run.size(), d_out, stream, false);
+    if (r) return r;
+    vi.clear();  // one launch over every rebuilt slice of every object
+    for (size_t i : run_of) {
+        uint64_t j = 0;
+        for (uint32_t sl = 0; sl < n; sl++)
+            if ((objs[i].lost_mask >> sl) & 1u)
+                vi.push_back(te_verify_item{objs[i].out_off + j++ * objs[i].slice_len, objs[i].slice_len, (uint32_t)(i * n + sl),
+                                            (uint32_t)i, 1u << sl, 0});
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    if ((r = verify_wait(c, d_out, vi, h_leaves, nobj * n, nobj, good.data(), s))) return r;
+    for (size_t i : run_of) h_ok_mask[i] = good[i] & objs[i].lost_mask;
+    return TE_OK;
+}
+
 int te_repair_verified_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair_object *objs,
                                     const uint8_t *h_leaves, size_t nobj, uint8_t *d_out, uint32_t *h_ok,
                                     void *stream) {
@@ -5429,11 +5569,11 @@ void read_resolve(const te_clay *c, ReadWin &W) {
 // its device current).  `objs` are te_decode_object or te_recover_object, by the fields they share
 // (slices_off, slice_len, avail_mask), their slices in h_in.  The caller gives what differs:
 // `dword`, its own conditions for device hashing besides slice_len % 4; `results`, that the window
-// goes on to verify one rebuilt slice per object in the same workspace; the stats and their upload
+// goes on to verify that many rebuilt slices in the same workspace (0: none); the stats and their upload
 // counter; `resolve`, run once W.good holds the final survivor sets; `upload`, the H2D copy runs.
 template <class Win, class Obj, class Stats, class Resolve, class Upload>
 int peer_stage_a(te_clay *c, WinPipe::Slot &sl, hipStream_t s, Win &W, const Obj *objs, const uint8_t *h_in, bool dword,
-                 bool results, Stats &st, uint64_t Stats::*uploaded, Resolve resolve, Upload upload) {
+                 size_t results, Stats &st, uint64_t Stats::*uploaded, Resolve resolve, Upload upload) {
     const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
     st.windows++;
     st.objects += W.nobj;
@@ -5486,7 +5626,7 @@ int peer_stage_a(te_clay *c, WinPipe::Slot &sl, hipStream_t s, Win &W, const Obj
     if (int r = upload(hin)) return r;
     if (!W.device_hash) return TE_OK;
     // verify_wait's launches without its wait, in the slot's own workspace
-    W.vl = VerLayout{W.nobj * n * TE_HASH_SIZE, vi.size() * TE_HASH_SIZE, results ? W.nobj * TE_HASH_SIZE : 0,
+    W.vl = VerLayout{W.nobj * n * TE_HASH_SIZE, vi.size() * TE_HASH_SIZE, results * TE_HASH_SIZE,
                      W.nobj * sizeof(uint32_t), results ? 2u : 1u};
     if (int r = ver_begin(sl.ver, sl.verh, W.vl, W.h_leaves, s)) return r;
     if (int r = ver_masks(c, sl.ver, sl.verh, sl.in.as<uint8_t>(), vi, W.vl, 0, s)) return r;
@@ -5501,7 +5641,7 @@ int read_stage_a(te_clay *c, WinPipe &P, int k, ReadWin &W) {
     WinPipe::Slot &sl = P.slot[k];
     const hipStream_t s = read_slot_stream(c, k);
     return peer_stage_a(
-        c, sl, s, W, W.objs, W.h_slices, true, false, c->rds, &te_read_launch_stats::slices_uploaded,
+        c, sl, s, W, W.objs, W.h_slices, true, 0, c->rds, &te_read_launch_stats::slices_uploaded,
         [&] { read_resolve(c, W); },
         [&](const std::vector<CopyRun> &hin) { return copy_runs(hin, sl.in.as<uint8_t>(), W.h_slices, hipMemcpyHostToDevice, s); });
 }
@@ -5897,6 +6037,8 @@ void recover_object_bytes(const te_clay *c, const te_recover_object *objs, size_
 struct RebuildWin {
     const te_repair_object *rep = nullptr;   // repair window
     const te_recover_object *rec = nullptr;  // recover window
+    const te_recover_multi_object *rm = nullptr;  // multi-slice recover window: L rebuilt slices per object, packed
+    te_recover_multi_stats *rms_sum = nullptr;    // ... its multi-kernel figures, summed over the call's windows
     te_slicer_cfg cfg{};
     const uint8_t *h_in = nullptr, *h_meta = nullptr, *h_leaves = nullptr;  // h_leaves null: unverified
     uint8_t *h_out = nullptr;
@@ -5916,7 +6058,9 @@ struct RebuildWin {
     std::vector<uint32_t> good;                  // recover: the slices that go up / rebuild from
     std::vector<size_t> run;                     // the objects that rebuild
     std::vector<uint64_t> out_dev, out_len, out_host;  // per object: its rebuilt slice on the device / host
-    std::vector<uint32_t> lost;
+    std::vector<uint32_t> lost;                  // the lost slice; a multi window: the lost mask
+    std::vector<uint32_t> avail;                 // recover: the caller's avail_mask and slice_len
+    std::vector<uint64_t> slen;
     std::vector<CopyRun> hout;
     uint64_t out_sz = 0;
     VerLayout vl{};  // device hashing: the slot's verify workspace
@@ -5953,7 +6097,7 @@ void recover_resolve(const te_clay *c, RebuildWin &W) {
     for (size_t o = 0; o < W.nobj; o++) {
         DecItem it{};
         // h_rej is written only when leaves were given
-        const int st = resolve_survivors(c, W.rec[o].avail_mask & all, W.rec[o].slice_len, W.h_meta + o * TE_META_SIZE,
+        const int st = resolve_survivors(c, W.avail[o] & all, W.slen[o], W.h_meta + o * TE_META_SIZE,
                                          W.pre ? W.pre[o] : TE_OK, W.good[o], W.h_leaves && W.h_rej ? W.h_rej + o : nullptr,
                                          W.h_status ? W.h_status + o : nullptr, W.good[o], it);
         if (W.h_leaves && W.h_ok) W.h_ok[o] = 0;  // unverified: h_ok is not the call's to write
@@ -5975,17 +6119,29 @@ int recover_stage_a(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
     W.out_len.resize(W.nobj);
     W.out_host.resize(W.nobj);
     W.lost.resize(W.nobj);
+    W.avail.resize(W.nobj);
+    W.slen.resize(W.nobj);
     bool dword = true;  // the recover kernels' and the rebuilt slice's verify item's alignment
-    for (size_t o = 0; o < W.nobj; o++) {
-        const te_recover_object &ob = W.rec[o];
-        W.out_len[o] = ob.slice_len;
+    size_t results = 0;
+    auto fill = [&](size_t o, const auto &ob, uint32_t lost, uint64_t nlost) {
+        W.out_len[o] = nlost * ob.slice_len;
         W.out_host[o] = ob.out_off;
-        W.lost[o] = ob.lost;
+        W.lost[o] = lost;
+        W.avail[o] = ob.avail_mask;
+        W.slen[o] = ob.slice_len;
+        results += nlost;
         dword = dword && ob.slices_off % 4u == 0 && ob.out_off % 4u == 0;
+    };
+    for (size_t o = 0; o < W.nobj; o++) {
+        if (W.rm) fill(o, W.rm[o], W.rm[o].lost_mask, (uint64_t)__builtin_popcount(W.rm[o].lost_mask));
+        else fill(o, W.rec[o], W.rec[o].lost, 1);
     }
-    return peer_stage_a(c, sl, s, W, W.rec, W.h_in, dword, true, c->rbs, &te_rebuild_launch_stats::pieces_uploaded,
-                        [&] { recover_resolve(c, W); },
-                        [&](const std::vector<CopyRun> &hin) { return rebuild_upload(c, sl, W, hin, s); });
+    auto stage = [&](const auto *objs) {
+        return peer_stage_a(c, sl, s, W, objs, W.h_in, dword, results, c->rbs, &te_rebuild_launch_stats::pieces_uploaded,
+                            [&] { recover_resolve(c, W); },
+                            [&](const std::vector<CopyRun> &hin) { return rebuild_upload(c, sl, W, hin, s); });
+    };
+    return W.rm ? stage(W.rm) : stage(W.rec);
 }
 
 // Stage A of a repair window: the plan's fragments, packed (each 16-byte aligned, as
@@ -6061,6 +6217,15 @@ int rebuild_stage_b(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
             for (size_t o = 0; o < W.nobj; o++)
                 items[o] = RepItem{W.rep[o].plan, W.frag_off.data() + o * n, W.out_dev[o], W.rep[o].metadata};
             if (int r = repair_enqueue(c, d_in, items.data(), items.size(), d_out, s)) return r;
+        } else if (W.rm) {  // the device form's routing (rec_multi_route), on the window's survivors
+            std::vector<te_recover_multi_object> objs;
+            std::vector<uint8_t> meta;
+            for (size_t o : W.run) {
+                objs.push_back(te_recover_multi_object{W.in_base[o], W.slen[o], W.good[o], W.lost[o], W.out_dev[o]});
+                meta.insert(meta.end(), W.h_meta + o * TE_META_SIZE, W.h_meta + (o + 1) * TE_META_SIZE);
+            }
+            if (int r = recover_multi_batch(c, &W.cfg, d_in, objs.data(), meta.data(), objs.size(), d_out, s, true, true)) return r;
+            rec_multi_stats_add(*W.rms_sum, c->rms);
         } else {
             std::vector<te_recover_object> objs;
             std::vector<uint8_t> meta;
@@ -6072,8 +6237,17 @@ int rebuild_stage_b(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
         }
         if (W.device_hash) {
             std::vector<te_verify_item> vi;
-            for (size_t o : W.run)
-                vi.push_back(te_verify_item{W.out_dev[o], W.out_len[o], (uint32_t)(o * n + W.lost[o]), (uint32_t)o, 1u, 0});
+            for (size_t o : W.run) {
+                if (!W.rm) {
+                    vi.push_back(te_verify_item{W.out_dev[o], W.out_len[o], (uint32_t)(o * n + W.lost[o]), (uint32_t)o, 1u, 0});
+                    continue;
+                }
+                uint64_t j = 0;  // the mask of object o gets the bit of each rebuilt slice that matches
+                for (uint32_t b = 0; b < n; b++)
+                    if ((W.lost[o] >> b) & 1u)
+                        vi.push_back(te_verify_item{W.out_dev[o] + j++ * W.slen[o], W.slen[o], (uint32_t)(o * n + b), (uint32_t)o,
+                                                    1u << b, 0});
+            }
             if (int r = ver_masks(c, sl.ver, sl.verh, d_out, vi, W.vl, 1, s)) return r;
             st.slices_hashed_device += vi.size();
         }
@@ -6105,16 +6279,30 @@ int rebuild_stage_c(te_clay *c, WinPipe &P, int k, RebuildWin &W, bool last) {
     if (!verified) return TE_OK;
     if (W.device_hash) {
         const uint32_t *m = reinterpret_cast<const uint32_t *>(sl.verh.u8() + W.vl.h_mask(1));
-        for (size_t o : W.run) W.h_ok[o] = m[o] & 1u;
+        for (size_t o : W.run) W.h_ok[o] = W.rm ? m[o] & W.lost[o] : m[o] & 1u;
         return TE_OK;
     }
     const size_t n = (size_t)c->h.n;
     std::vector<HashItem> items;
-    for (size_t o : W.run)
-        items.push_back({W.h_out + W.out_host[o], W.out_len[o], W.h_leaves + (o * n + W.lost[o]) * TE_HASH_SIZE});
+    std::vector<std::pair<size_t, uint32_t>> who;  // the item's object and the value its match adds to h_ok
+    for (size_t o : W.run) {
+        if (!W.rm) {
+            items.push_back({W.h_out + W.out_host[o], W.out_len[o], W.h_leaves + (o * n + W.lost[o]) * TE_HASH_SIZE});
+            who.push_back({o, 1u});
+            continue;
+        }
+        uint64_t j = 0;
+        for (uint32_t b = 0; b < (uint32_t)n; b++)
+            if ((W.lost[o] >> b) & 1u) {
+                items.push_back({W.h_out + W.out_host[o] + j++ * W.slen[o], W.slen[o], W.h_leaves + (o * n + b) * TE_HASH_SIZE});
+                who.push_back({o, 1u << b});
+            }
+    }
     std::vector<uint8_t> ok;
     hash_items_host(items, c->device, ok);
-    for (size_t j = 0; j < W.run.size(); j++) W.h_ok[W.run[j]] = ok[j];
+    for (size_t o : W.run) W.h_ok[o] = 0;  // a repair window's h_ok is first written here: whatever the caller left goes
+    for (size_t j = 0; j < items.size(); j++)
+        if (ok[j]) W.h_ok[who[j].first] |= who[j].second;
     st.slices_hashed_host += items.size();
     return TE_OK;
 }
@@ -6275,6 +6463,82 @@ int te_recover_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h
         W.copy_only = copy_only;
     }
     return rebuild_run(c, wins);
+}
+
+int te_recover_multi_window_plan(const te_clay *c, const te_recover_multi_object *objs, size_t nobj, size_t window_bytes,
+                                 size_t *cuts, size_t cap, size_t *nwindows) {
+    if (!c || !nwindows || (!objs && nobj)) return TE_ERR_INVALID_ARG;
+    *nwindows = 0;
+    std::vector<uint64_t> bytes(nobj);
+    for (size_t i = 0; i < nobj; i++)
+        bytes[i] = rec_multi_object_bytes(c->h.n, objs[i].avail_mask, objs[i].lost_mask, objs[i].slice_len);
+    std::vector<size_t> v;
+    window_cuts(bytes, window_bytes, v);
+    return cuts_out(v, cuts, cap, nwindows);
+}
+
+int te_recover_multi_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices,
+                                const te_recover_multi_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
+                                size_t nobj, uint8_t *h_out, uint32_t *h_rejected_mask, uint32_t *h_ok_mask, int *h_status,
+                                size_t window_bytes) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_slices || !h_out) && nobj)) return TE_ERR_INVALID_ARG;
+    const bool verified = h_leaves != nullptr;
+    if (verified && (!h_status || !h_ok_mask) && nobj) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n;
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    std::vector<int> pre(nobj, TE_OK);
+    std::vector<uint64_t> bytes(nobj);
+    for (size_t i = 0; i < nobj; i++) {
+        RecMultiItem m{};
+        const int r = rec_multi_validate(c, objs[i], h_meta + i * TE_META_SIZE, m);
+        if (r && !(verified && r == TE_ERR_NOT_ENOUGH_SLICES)) return r;
+        pre[i] = r;
+        bytes[i] = rec_multi_object_bytes(c->h.n, objs[i].avail_mask, objs[i].lost_mask, objs[i].slice_len);
+    }
+    std::vector<size_t> cuts;
+    window_cuts(bytes, window_bytes, cuts);
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->els = te_encode_launch_stats{};
+    c->rbs = te_rebuild_launch_stats{};
+    c->rms = te_recover_multi_stats{};
+    if (nobj == 0) return TE_OK;
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    // as te_recover_batch_host: h_slices is asked of the first present slice
+    bool pin_in = true;
+    for (size_t i = 0; i < nobj; i++)
+        if (const uint32_t m = objs[i].avail_mask & slice_bits(c)) {
+            pin_in = host_pinned(h_slices + objs[i].slices_off + (uint64_t)__builtin_ctz(m) * objs[i].slice_len);
+            break;
+        }
+    const bool pin_out = host_pinned(h_out), copy_only = rebuild_copy_only();
+    te_recover_multi_stats sum{};
+    std::vector<RebuildWin> wins(cuts.size() - 1);
+    for (size_t w = 0; w < wins.size(); w++) {
+        RebuildWin &W = wins[w];
+        const size_t a = cuts[w];
+        W.rm = objs + a;
+        W.rms_sum = &sum;
+        W.cfg = *cfg;
+        W.h_in = h_slices;
+        W.h_out = h_out;
+        W.h_meta = h_meta + a * TE_META_SIZE;
+        W.h_leaves = verified ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
+        W.nobj = cuts[w + 1] - a;
+        W.h_rej = h_rejected_mask ? h_rejected_mask + a : nullptr;
+        W.h_ok = h_ok_mask ? h_ok_mask + a : nullptr;
+        W.h_status = h_status ? h_status + a : nullptr;
+        W.pre = pre.data() + a;
+        W.mode = g_commit_hashing.load();
+        W.pinned_in = pin_in;
+        W.pinned_out = pin_out;
+        W.copy_only = copy_only;
+    }
+    const int r = rebuild_run(c, wins);
+    c->rms = sum;
+    return r;
 }
 
 int te_clay_rebuild_launch_stats(te_clay *c, te_rebuild_launch_stats *out) {

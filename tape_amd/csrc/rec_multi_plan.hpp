@@ -37,6 +37,14 @@ inline int rec_multi_check(int n, int k, uint32_t avail, uint32_t lost) {
     return TE_OK;
 }
 
+// ---- the host pipeline's windows (te_recover_multi_window_plan) ----
+// What an object counts towards window_cuts' limit (win_plan.hpp): its present slices in and its
+// lost slices out, a slice length each.  Bits at or above n count for nothing.
+inline uint64_t rec_multi_object_bytes(int n, uint32_t avail, uint32_t lost, uint64_t slice_len) {
+    const uint32_t all = n >= 32 ? 0xffffffffu : (1u << n) - 1u;
+    return ((uint64_t)__builtin_popcount(avail & all) + (uint64_t)__builtin_popcount(lost & all)) * slice_len;
+}
+
 // ---- a stripe's lost nodes and output table ----
 // The internal nodes the lost slices hold in stripe st (the rotation moves them per stripe).  The
 // survivors follow the decode's rule (stripe_emask: the absent shards padded by A7 to n - k

@@ -636,9 +636,15 @@ class Slicer:
         _check(r, "decode")
         return bytes(out)[:got.value]
 
-    def recover_many(self, slices: list[tuple[int, bytes]], lost: list[int]) -> dict[int, bytes]:
+    def recover_many(self, slices: list[tuple[int, bytes]], lost: list[int], leaves=None):
         """te_slicer_recover_multi: `reconstruct` (recover.rs:411-442) for several lost slices of one
-        object -- the peers' slices go to the device once, every slice index in `lost` comes back."""
+        object -- the peers' slices go to the device once, every slice index in `lost` comes back.
+        With leaves (the object's n leaf hashes: n * 32 bytes, or a list of n hashes) the call runs
+        te_recover_multi_batch_host's verified form on the one object (recover.rs:207-218) and returns
+        (slices, ok_mask, rejected_mask): peers that fail their leaf are left out and reported, ok_mask
+        has the bit of each rebuilt slice that matches its leaf (the bytes are returned either way)."""
+        if leaves is not None:
+            return self._recover_many_verified(slices, lost, leaves)
         if not slices:
             raise DecodeError("NotEnoughSlices")
         n = self.n()
@@ -661,6 +667,39 @@ class Slicer:
                                         sum(1 << i for i in want), optrs)
         _check(r, "recover")
         return {i: bytes(o)[:slice_len] for i, o in zip(want, outs)}
+
+    def _recover_many_verified(self, slices, lost, leaves):
+        if not slices:
+            raise DecodeError("NotEnoughSlices")
+        n = self.n()
+        slice_len = len(slices[0][1])
+        want = sorted(set(lost))
+        if not want or len(want) != len(lost) or not all(0 <= i < n for i in want):
+            raise ValueError("lost: distinct slice indices below n")
+        lb = bytes(leaves) if isinstance(leaves, (bytes, bytearray, memoryview)) else b"".join(bytes(h) for h in leaves)
+        if len(lb) != n * 32:
+            raise ValueError(f"leaves: {len(lb)} bytes, expected {n} x 32")
+        src = (C.c_uint8 * max(1, n * slice_len))()
+        avail = 0
+        for idx, data in slices:
+            if not (0 <= idx < n) or len(data) != slice_len or avail >> idx & 1:
+                raise DecodeError("InvalidLayout")
+            C.memmove(C.byref(src, idx * slice_len), bytes(data), slice_len)
+            avail |= 1 << idx
+        if slice_len < 48:
+            raise DecodeError("InvalidLayout")
+        obj = _lib.te_recover_multi_object(0, slice_len, avail, sum(1 << i for i in want), 0)
+        meta = (C.c_uint8 * 48).from_buffer_copy(bytes(slices[0][1])[-48:])
+        out = (C.c_uint8 * max(1, len(want) * slice_len))()
+        rej, ok, st = C.c_uint32(), C.c_uint32(), C.c_int()
+        cfg = self._cfg()
+        r = lib.te_recover_multi_batch_host(self.coder.handle, C.byref(cfg), C.cast(src, C.c_void_p), C.byref(obj), meta,
+                                            (C.c_uint8 * len(lb)).from_buffer_copy(lb), 1, C.cast(out, C.c_void_p),
+                                            C.byref(rej), C.byref(ok), C.byref(st), 0)
+        _check(r, "recover")
+        _check(st.value, "recover")
+        raw = bytes(out)
+        return ({i: raw[j * slice_len:(j + 1) * slice_len] for j, i in enumerate(want)}, int(ok.value), int(rej.value))
 
     def decode_range(self, chunks: list[tuple[int, bytes]], start: int, length: int) -> bytes:
         """te_slicer_decode_range: Slicer::decode followed by bytes[start..start + length] (the
