@@ -617,7 +617,12 @@ int te_merkle_verify_leaf_hash(const uint8_t leaf_hash[TE_HASH_SIZE], const uint
 /* Batched commitments on the device (DEVICE pointers, enqueued on hip_stream): object o's n
  * slices at d_slices + o*obj_stride + i*slice_len (slice_len % 4 == 0, n <= 64) ->
  * leaf hashes d_leaf_hashes[(o*n + i)*32], roots d_roots[o*32] (NULL: leaves only), proofs
- * d_proofs[((o*n + i)*height + level)*32] (NULL: none). */
+ * d_proofs[((o*n + i)*height + level)*32] (NULL: none).  The slices are read as 32-bit words:
+ * a d_slices that is not 4-byte aligned, or an obj_stride or slice_len that is no multiple of 4, is
+ * TE_ERR_INVALID_ARG, as are n == 0, n > 64, a NULL d_slices or d_leaf_hashes, d_proofs without
+ * d_roots and, with d_roots, a height of 0 or above 32; n > 2^height with d_roots is
+ * TE_ERR_MERKLE_TREE_FULL.  All of these are decided before any device call, and nothing is
+ * written.  nobj == 0 is TE_OK and writes nothing. */
 int te_commit_batch_device(const uint8_t *d_slices, uint64_t obj_stride, uint64_t slice_len, uint32_t n,
                            size_t nobj, uint32_t height, uint8_t *d_leaf_hashes, uint8_t *d_roots,
                            uint8_t *d_proofs, void *hip_stream);
@@ -1106,6 +1111,7 @@ size_t te_snapshot_work_bytes(const te_clay *c, uint64_t compressed_len, uint32_
 /* encode_snapshot's compute (encode.rs:62-154) on the device, enqueued on hip_stream; returns
  * without waiting.  d_compressed: `len` bytes at ANY byte address.  Outputs (DEVICE):
  *   d_slices       plan.total_slice_bytes, laid out as te_snapshot_segment.slices_off says;
+ *                  4-byte aligned when d_leaf_hashes is given (TE_ERR_INVALID_ARG otherwise);
  *   d_leaf_hashes  chunk t's 20 leaves at (t * n_inner + i) * 32; NULL: no commitments;
  *   d_roots        chunk t's root (tree height TE_SLICE_TREE_HEIGHT) at t * 32; NULL: leaves only;
  *   d_work         te_snapshot_work_bytes of scratch, 64-byte aligned (TE_ERR_INVALID_ARG

@@ -144,7 +144,9 @@ __global__ void __launch_bounds__(64) tree_kernel(CommitArgs a) {
 
 hipError_t launch_commit(const CommitArgs &a, hipStream_t s) {
     if (a.nobj == 0 || a.n == 0) return hipSuccess;
-    if (a.n > (uint32_t)kCommitMaxLeaves || a.slice_len % 4u || !a.leaf) return hipErrorInvalidValue;
+    if (a.n > (uint32_t)kCommitMaxLeaves || a.slice_len % 4u || a.obj_stride % 4u ||
+        (reinterpret_cast<uintptr_t>(a.slices) & 3u) || !a.leaf)
+        return hipErrorInvalidValue;
     const uint64_t total = (uint64_t)a.nobj * a.n;
     const uint64_t T = ((uint64_t)a.slice_len + 4u + 8u) / 64u + 1u;  // blocks per stream
     const uint64_t nl = (T + commit::kLeafBlocksPerLaunch - 1) / commit::kLeafBlocksPerLaunch, per = (T + nl - 1) / nl;

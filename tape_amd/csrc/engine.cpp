@@ -4690,8 +4690,9 @@ int te_commit_batch_device(const uint8_t *d_slices, uint64_t obj_stride, uint64_
                            size_t nobj, uint32_t height, uint8_t *d_leaf_hashes, uint8_t *d_roots,
                            uint8_t *d_proofs, void *stream) {
     if (nobj == 0) return TE_OK;
-    if (!d_slices || !d_leaf_hashes || n == 0 || n > TE_COMMIT_MAX_LEAVES || slice_len % 4 ||
-        nobj > 0xffffffffull / n || ((d_roots || d_proofs) && (height == 0 || height > TE_MAX_MERKLE_TREE_HEIGHT)) ||
+    // the leaf kernel reads every slice as dwords: its base, its length and the object stride are 4-aligned
+    if (!d_slices || !d_leaf_hashes || n == 0 || n > TE_COMMIT_MAX_LEAVES || slice_len % 4 || obj_stride % 4 ||
+        (reinterpret_cast<uintptr_t>(d_slices) & 3u) || nobj > 0xffffffffull / n || ((d_roots || d_proofs) && (height == 0 || height > TE_MAX_MERKLE_TREE_HEIGHT)) ||
         (d_proofs && !d_roots))
         return TE_ERR_INVALID_ARG;
     if ((d_roots || d_proofs) && height < 64 && (uint64_t)n > (1ull << height)) return TE_ERR_MERKLE_TREE_FULL;
@@ -7333,8 +7334,10 @@ size_t te_snapshot_work_bytes(const te_clay *c, uint64_t compressed_len, uint32_
 int te_snapshot_encode_device(te_clay *c, const uint8_t *d_compressed, uint64_t len, uint32_t total_groups,
                               uint8_t *d_slices, uint8_t *d_leaf_hashes, uint8_t *d_roots, uint8_t *d_work,
                               size_t work_bytes, void *stream) {
+    // d_slices is the commit step's input (te_commit_batch_device: 4-aligned), refused here, before
+    // the pack and the encode are enqueued, not after them
     if (!c || (!d_compressed && len) || !d_slices || !d_work || (d_roots && !d_leaf_hashes) ||
-        (reinterpret_cast<uintptr_t>(d_work) & 63u))
+        (reinterpret_cast<uintptr_t>(d_work) & 63u) || (d_leaf_hashes && (reinterpret_cast<uintptr_t>(d_slices) & 3u)))
         return TE_ERR_INVALID_ARG;
     SnapPlan P;
     int r = snap_plan(c, len, total_groups, P);

@@ -328,8 +328,8 @@ hipError_t launch_dec_class(int id, const GpeJob *jobs, const GpePattern *patter
 // ---- slice commitments (commit.hip) ----
 constexpr int kCommitMaxLeaves = 64;
 struct CommitArgs {
-    const uint8_t *slices;     // object o's slice i at slices + o * obj_stride + i * slice_len
-    uint64_t obj_stride, slice_len;  // slice_len % 4 == 0
+    const uint8_t *slices;     // object o's slice i at slices + o * obj_stride + i * slice_len; 4-aligned
+    uint64_t obj_stride, slice_len;  // both % 4 == 0 (launch_commit refuses anything else)
     uint32_t n, nobj, height;
     uint8_t *leaf;             // nobj * n * 32
     uint8_t *root;             // nobj * 32, or null (no tree)

@@ -1,7 +1,8 @@
 """Slice commitments: oracle pinned by the reference's EMPTY_ROOTS, libtapeec's host
 merkle entry points against the oracle, and the reference's own merkle tests
 (lib/crypto/src/merkle/tree.rs:488-841) restated.  CPU only (the batch kernel is in
-test_gpu_parity.py)."""
+test_gpu_parity.py at the production shape and in test_gpu_commit_edges.py at its shape edges; the
+argument checks of its device call are in test_commit_edge_cases.py)."""
 import json
 import os
 import random
