@@ -94,7 +94,7 @@ inline uint64_t dec_key_emask(uint64_t key) { return key % kDecKeyNode; }
 inline int dec_key_out_node(uint64_t key) { return (int)(key / kDecKeyNode) - 1; }
 
 // The staged and class kernels read sub-chunks of >= 8 bytes and address a stripe's slices and its
-// output share with 31-bit offsets: decode_enqueue, range_chunk_ok and recover_batch answer from this.
+// output share with 31-bit offsets: decode_enqueue, range_chunk_ok and rec_route answer from this.
 inline bool dec_geom_staged(const ClayHost &h, uint64_t cs, uint64_t slice_len) {
     constexpr uint64_t lim = 0x7fffffffull;
     return cs / (uint64_t)h.alpha >= 8 && (uint64_t)h.n * slice_len < lim && cs * (uint64_t)h.k < lim;

@@ -3450,227 +3450,6 @@ int te_repair_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair
     return repair_enqueue(c, d_helpers, items.data(), items.size(), d_out, (hipStream_t)stream);
 }
 
-// Node recover (network/node/src/features/spool/recover.rs:411-442 `reconstruct`): decode the
-// object from >= k peer slices, re-encode it, keep the lost slice.  Per stripe the lost slice
-// holds one shard (rotation): a data shard is a piece of the decoded object (zero-padded like
-// Slicer::encode's stripe, slicer.rs:276-283), so only stripes whose lost shard is a parity
-// shard are re-encoded.  Objects go through the device workspaces in windows (bounded memory);
-// the workspaces are ordered against a previous call on another stream by `rec_done`.
-}  // extern "C"
-// later calls (any stream) order against everything this one enqueued on s
-static int rec_mark_done(te_clay *c, hipStream_t s) {
-    if (!c->rec_done) TE_HIP(hipEventCreateWithFlags(&c->rec_done, hipEventDisableTiming));
-    const int r = hip_status(hipEventRecord(c->rec_done, s));
-    c->rec_pending = true;
-    c->rec_stream = s;
-    return r;
-}
-// part = a subset of a mixed batch, called from the whole batch's call: the launch stats go on summing
-// locked = the caller holds the handle's lock (the host rebuild pipeline)
-static int recover_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_object *objs,
-                         const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool part,
-                         bool locked = false) {
-    if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
-    if (nobj == 0) return TE_OK;
-    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
-    if (!part) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        c->dls = te_decode_launch_stats{};
-        c->els = te_encode_launch_stats{};  // the keep-filter re-encode of the parity-lost stripes
-    }
-    const ClayHost &h = c->h;
-    const uint32_t n = (uint32_t)h.n;
-    const int rotated = cfg->rotated;
-    std::vector<DecItem> items(nobj);
-    std::vector<te_object> enc(nobj);
-    std::vector<uint64_t> stripe(nobj), nstripes(nobj), chunk(nobj), meta_w(nobj * 6);
-    for (size_t i = 0; i < nobj; i++) {
-        if (objs[i].lost >= n) return TE_ERR_INVALID_SLICE;
-        int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, items[i]);
-        if (r) return r;
-        te_slice_metadata m;
-        te_slice_metadata_from_slice(h_meta + i * TE_META_SIZE, TE_META_SIZE, &m);
-        te_geometry g;
-        te_slicer_geometry(c, items[i].blob_len, &g);
-        if (g.slice_len != objs[i].slice_len) return TE_ERR_INVALID_LAYOUT;
-        items[i].in_base = objs[i].slices_off;
-        enc[i] = te_object{0, items[i].blob_len, 0, m.chunk_index};
-        stripe[i] = g.stripe_size;
-        nstripes[i] = g.num_stripes;  // an empty blob still has one (all-zero) stripe
-        chunk[i] = g.chunk_size;
-        for (int w = 0; w < 6; w++) meta_w[i * 6 + w] = get_u64(h_meta + i * TE_META_SIZE + 8 * w);
-    }
-    auto meta_job = [&](size_t i, uint8_t *dst) {  // object i's metadata suffix, written at dst
-        MetaJob m{};
-        m.dst = dst;
-        for (int k = 0; k < 6; k++) m.words[k] = meta_w[i * 6 + k];
-        return m;
-    };
-    // A mixed batch goes in two parts: the objects the fused path takes (a plane-program profile
-    // and a geometry the staged kernels address: dec_geom_staged) and the rest,
-    // so one small object does not send the whole batch to the windowed decode + re-encode
-    // (ADVICE r03).  Offsets are absolute, so each part is the same call on a subset.
-    {
-        const bool planes = h.q == kRepQ && h.t == 2 && h.nu == 0;
-        std::vector<size_t> part[2];
-        for (size_t i = 0; i < nobj; i++) {
-            // (an empty blob has no stripe to decode: its one all-zero chunk is short)
-            const bool fz = planes && (items[i].ns == 0 || dec_geom_staged(h, chunk[i], objs[i].slice_len));
-            part[fz ? 0 : 1].push_back(i);
-        }
-        if (!part[0].empty() && !part[1].empty()) {
-            for (const auto &pv : part) {
-                std::vector<te_recover_object> o;
-                std::vector<uint8_t> m;
-                for (size_t i : pv) {
-                    o.push_back(objs[i]);
-                    m.insert(m.end(), h_meta + i * TE_META_SIZE, h_meta + (i + 1) * TE_META_SIZE);
-                }
-                const int r = recover_batch(c, cfg, d_slices, o.data(), m.data(), o.size(), d_out, stream, true, locked);
-                if (r) return r;
-            }
-            return TE_OK;
-        }
-    }
-    {
-        // Fused: one staged decode whose program outputs only the lost node's chunk of every stripe,
-        // straight into the lost slice -- 7 slices read, 1 written, no decoded object and no
-        // re-encode (a lost parity node's C is produced by the same layered decode).  Empty blobs
-        // have no stripe to decode: their one chunk is zeros.
-        std::vector<DecItem> fi(items);
-        std::vector<CopyJob> zeros;
-        std::vector<MetaJob> metas;
-        for (size_t i = 0; i < nobj; i++) {
-            fi[i].lost = (int32_t)objs[i].lost;
-            fi[i].out_off = objs[i].out_off;
-            uint8_t *dst = d_out + objs[i].out_off;
-            if (items[i].ns == 0) zeros.push_back(CopyJob{d_out, dst, chunk[i] * nstripes[i], 0});
-            metas.push_back(meta_job(i, dst + nstripes[i] * chunk[i]));
-        }
-        std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
-        if (!locked) lk.lock();
-        DeviceGuard dg(c->device);
-        TE_HIP(dg.err);
-        hipStream_t s = (hipStream_t)stream;
-        const int rf = decode_enqueue(c, cfg, d_slices, fi.data(), nobj, d_out, s, false);
-        if (rf != TE_ERR_UNSUPPORTED) {
-            if (rf) return rf;
-            if (c->rec_pending && c->rec_stream != s) TE_HIP(hipStreamWaitEvent(s, c->rec_done, 0));
-            const int r = gather_meta_enqueue(c->rec, s, zeros, metas), r2 = rec_mark_done(c, s);
-            return r ? r : r2;
-        }
-    }
-    // Otherwise (profiles without plane programs): windowed decode into the object, re-encode of
-    // the parity-lost stripes, gather.
-    auto is_parity = [&](size_t i, size_t st) {
-        return te_slice_to_shard(rotated, n, (uint32_t)st, objs[i].lost) >= (uint32_t)h.k;
-    };
-    // windows: <= kWinBlob decoded bytes and <= kWinSlices re-encoded slice bytes
-    uint64_t kWinBlob = 1ull << 30, kWinSlices = 3ull << 30;
-    if (const char *e = tec_knob("TEC_RECOVER_WINDOW_BYTES")) {  // tests: force several windows
-        const uint64_t v = strtoull(e, nullptr, 10);
-        if (v) kWinBlob = kWinSlices = v;
-    }
-    struct Win { size_t b, e; uint64_t blob, slices; };
-    std::vector<Win> wins;
-    uint64_t max_blob = 16, max_slices = 16;
-    for (size_t i = 0; i < nobj;) {
-        Win w{i, i, 0, 0};
-        while (w.e < nobj) {
-            const uint64_t bb = align16(items[w.e].blob_len), sb = (uint64_t)n * objs[w.e].slice_len;
-            if (w.e > w.b && (w.blob + bb > kWinBlob || w.slices + sb > kWinSlices)) break;
-            w.blob += bb;
-            w.slices += sb;
-            w.e++;
-        }
-        max_blob = std::max(max_blob, w.blob + 16);
-        max_slices = std::max(max_slices, w.slices + 16);
-        wins.push_back(w);
-        i = w.e;
-    }
-    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
-    if (!locked) lk.lock();
-    DeviceGuard dg(c->device);
-    TE_HIP(dg.err);
-    hipStream_t s = (hipStream_t)stream;
-    if (max_blob > c->rec_blob.cap || max_slices > c->rec_slices.cap) {
-        if (c->rec_pending) TE_HIP(hipEventSynchronize(c->rec_done));  // queued work may still use them
-    } else if (c->rec_pending && c->rec_stream != s) {
-        TE_HIP(hipStreamWaitEvent(s, c->rec_done, 0));
-    }
-    TE_HIP(c->rec_blob.ensure(max_blob));
-    TE_HIP(c->rec_slices.ensure(max_slices));
-    uint8_t *const blob = c->rec_blob.as<uint8_t>(), *const slices = c->rec_slices.as<uint8_t>();
-    std::vector<CopyJob> jobs;
-    std::vector<MetaJob> metas;
-    std::vector<te_object> wenc;
-    std::vector<uint64_t> blob_off;
-    int r = TE_OK;
-    for (const Win &w : wins) {
-        blob_off.assign(w.e - w.b, 0);
-        wenc.clear();
-        uint64_t bo = 0, so = 0;
-        for (size_t i = w.b; i < w.e; i++) {
-            items[i].out_off = bo;
-            blob_off[i - w.b] = bo;
-            te_object e = enc[i];
-            e.data_off = bo;
-            e.out_off = so;
-            wenc.push_back(e);
-            bo += align16(items[i].blob_len);
-            so += (uint64_t)n * objs[i].slice_len;
-        }
-        if ((r = decode_enqueue(c, cfg, d_slices, items.data() + w.b, w.e - w.b, blob, s, false))) break;
-        bool any_parity = false;
-        for (size_t i = w.b; i < w.e && !any_parity; i++)
-            for (uint64_t st = 0; st < nstripes[i]; st++) any_parity = any_parity || is_parity(i, st);
-        // parity-lost stripes are re-encoded writing only the lost shard's chunk (plus the
-        // column-0 parity chunks the LDS-DMA kernel reads back internally)
-        const uint32_t col0_parity = ((1u << h.q) - 1u) & ~((1u << h.k) - 1u);
-        if (any_parity &&
-            (r = encode_enqueue(c, cfg, blob, wenc.data(), wenc.size(), slices, s, false, nullptr,
-                                [&](size_t o, size_t st) -> uint32_t {
-                                    if (!is_parity(w.b + o, st)) return 0u;
-                                    return col0_parity | (1u << te_slice_to_shard(rotated, n, (uint32_t)st,
-                                                                                  objs[w.b + o].lost));
-                                })))
-            break;
-        // assemble the lost slices: per stripe the lost shard's chunk, then the suffix
-        jobs.clear();
-        metas.clear();
-        for (size_t i = w.b; i < w.e; i++) {
-            const DecItem &it = items[i];
-            const uint64_t cs = chunk[i], slen = objs[i].slice_len, ns = nstripes[i];
-            uint8_t *dst = d_out + objs[i].out_off;
-            for (uint64_t st = 0; st < ns; st++) {
-                const uint32_t sh = te_slice_to_shard(rotated, n, (uint32_t)st, objs[i].lost);
-                if (sh >= (uint32_t)h.k) {
-                    jobs.push_back(CopyJob{slices + wenc[i - w.b].out_off + (uint64_t)objs[i].lost * slen + st * cs,
-                                           dst + st * cs, cs, cs});
-                } else {
-                    // data shard sh of stripe st: object bytes [st*S + sh*cs, ...) clipped to the
-                    // stripe and the object, zero beyond
-                    const uint64_t start = st * stripe[i] + (uint64_t)sh * cs;
-                    const uint64_t end = std::min<uint64_t>(it.blob_len, (st + 1) * stripe[i]);
-                    const uint64_t valid = start < end ? std::min<uint64_t>(cs, end - start) : 0;
-                    jobs.push_back(CopyJob{blob + blob_off[i - w.b] + std::min(start, it.blob_len), dst + st * cs, cs, valid});
-                }
-            }
-            metas.push_back(meta_job(i, dst + ns * cs));
-        }
-        if ((r = gather_meta_enqueue(c->rec, s, jobs, metas))) break;
-    }
-    const int r2 = rec_mark_done(c, s);
-    return r ? r : r2;
-}
-extern "C" {
-
-int te_recover_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
-                            const te_recover_object *objs, const uint8_t *h_meta, size_t nobj, uint8_t *d_out,
-                            void *stream) {
-    return recover_batch(c, cfg, d_slices, objs, h_meta, nobj, d_out, stream, false);
-}
-
 int te_slicer_encode(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *data, size_t len, uint8_t *slices,
                      size_t cap) {
     if (!c || !cfg || (!data && len) || !slices) return TE_ERR_INVALID_ARG;
@@ -3807,34 +3586,33 @@ static int percall_decode_device(te_clay *c, const te_slicer_cfg *cfg, const Dec
 }
 
 // ------------------------------------------------------------------------------------------
-// Multi-output rebuild (te_recover_multi_batch_device, recover.rs:411-442 for several slices of
-// one object): rec_multi_plan.hpp has the rules, recover_multi.hip the kernel
+// Node recover (network/node/src/features/spool/recover.rs:411-442 `reconstruct`): rebuild the lost
+// slices of an object from >= k peer slices.  One lost slice (te_recover_object) is a lost mask of
+// one bit (te_recover_multi_object): every entry point validates its objects into RecItem and
+// routes them by rec_multi_plan.hpp's rec_route -- the class path, the multi-output kernel
+// (recover_multi.hip) or the generic path (decode, re-encode, keep the lost slices).
 // ------------------------------------------------------------------------------------------
 namespace {
-struct RecMultiItem {
+struct RecItem {
     DecItem it;        // validated like Slicer::decode; in_base set
     uint32_t lost;     // the lost slices
     uint64_t out_off;  // the j-th of them at d_out + out_off + j * it.slice_len
-    uint64_t cs, ns;   // the slices' chunk size and stripes (an empty blob: one zero chunk)
+    uint64_t cs, ns, stripe;  // the slices' chunk size, stripes (an empty blob: one zero chunk) and stripe size
     uint64_t chunk_index, meta_w[6];
 };
 
-// A window's figures into its call's (te_recover_multi_batch_host): sums, and the most passes
-void rec_multi_stats_add(te_recover_multi_stats &sum, const te_recover_multi_stats &w) {
-    sum.multi_launches += w.multi_launches;
-    sum.passes = std::max(sum.passes, w.passes);
-    sum.jobs += w.jobs;
-    sum.out_rows += w.out_rows;
-    sum.stripes += w.stripes;
-    sum.split_stripes += w.split_stripes;
-    sum.single_objects += w.single_objects;
-    sum.generic_objects += w.generic_objects;
-    sum.multi_objects += w.multi_objects;
+// A single-slice entry point's object as the one form: its lost index is a one-bit mask.  These
+// entry points ask only lost < n (an empty mask here, rec_validate's TE_ERR_INVALID_SLICE): not
+// that the lost slice is absent, as the multi forms do.
+te_recover_multi_object rec_single(const te_clay *c, const te_recover_object &o) {
+    return te_recover_multi_object{o.slices_off, o.slice_len, o.avail_mask, o.lost < (uint32_t)c->h.n ? 1u << o.lost : 0u,
+                                   o.out_off};
 }
 
-// One object's checks, host only: the masks, then Slicer::decode's, then the slice length
-int rec_multi_validate(const te_clay *c, const te_recover_multi_object &o, const uint8_t *meta48, RecMultiItem &m) {
-    int r = rec_multi_check(c->h.n, c->h.k, o.avail_mask, o.lost_mask);
+// One object's checks, host only: the mask by its entry point's rule (single = rec_single's, else
+// rec_multi_check), then Slicer::decode's, then the slice length
+int rec_validate(const te_clay *c, const te_recover_multi_object &o, const uint8_t *meta48, bool single, RecItem &m) {
+    int r = single ? (o.lost_mask ? TE_OK : TE_ERR_INVALID_SLICE) : rec_multi_check(c->h.n, c->h.k, o.avail_mask, o.lost_mask);
     if (r || (r = decode_validate(c, meta48, o.slice_len, o.avail_mask, m.it))) return r;
     te_slice_metadata md;
     te_slice_metadata_from_slice(meta48, TE_META_SIZE, &md);
@@ -3846,9 +3624,29 @@ int rec_multi_validate(const te_clay *c, const te_recover_multi_object &o, const
     m.out_off = o.out_off;
     m.cs = g.chunk_size;
     m.ns = g.num_stripes;
+    m.stripe = g.stripe_size;
     m.chunk_index = md.chunk_index;
     for (int w = 0; w < 6; w++) m.meta_w[w] = get_u64(meta48 + 8 * w);
     return TE_OK;
+}
+
+// The metadata suffix of m's j-th rebuilt slice
+MetaJob rec_meta(const RecItem &m, uint8_t *d_out, uint64_t j) {
+    MetaJob mj{};
+    mj.dst = d_out + m.out_off + j * m.it.slice_len + m.ns * m.cs;
+    for (int k = 0; k < 6; k++) mj.words[k] = m.meta_w[k];
+    return mj;
+}
+
+// The recover workspaces (rec_blob, rec_slices, the gather arena) are ordered against a previous
+// call on another stream by `rec_done`: later calls (any stream) order against everything this
+// one enqueued on s
+int rec_mark_done(te_clay *c, hipStream_t s) {
+    if (!c->rec_done) TE_HIP(hipEventCreateWithFlags(&c->rec_done, hipEventDisableTiming));
+    const int r = hip_status(hipEventRecord(c->rec_done, s));
+    c->rec_pending = true;
+    c->rec_stream = s;
+    return r;
 }
 
 // The sub-masks of a stripe's (padded erasure mask, lost nodes) and their programs, compiled once
@@ -3899,14 +3697,14 @@ const std::vector<uint64_t> *rec_multi_subs(te_clay *c, uint64_t emask, uint64_t
 // before the call enqueues, on up to 16 host threads as dec_precompile's patterns are (a first-time
 // pair is about a millisecond of host work: the split tries a program per part and orientation).
 // rec_multi_subs then finds every pair of the call in the cache.  Caller holds c->mu.
-void rec_multi_precompile(te_clay *c, int rotated, const std::vector<RecMultiItem> &items) {
+void rec_multi_precompile(te_clay *c, int rotated, const std::vector<const RecItem *> &items) {
     const ClayHost &h = c->h;
     std::vector<std::pair<uint64_t, uint64_t>> todo;
     std::unordered_set<uint64_t> seen;
-    for (const RecMultiItem &m : items)
-        for (uint64_t st = 0; st < m.it.ns; st++) {
-            const uint64_t emask = stripe_emask(h, rotated, m.it.avail, st);
-            const uint64_t lostn = rec_multi_lost_nodes(h, rotated, m.lost, st);
+    for (const RecItem *p : items)
+        for (uint64_t st = 0; st < p->it.ns; st++) {
+            const uint64_t emask = stripe_emask(h, rotated, p->it.avail, st);
+            const uint64_t lostn = rec_multi_lost_nodes(h, rotated, p->lost, st);
             const uint64_t key = rec_multi_key(emask, lostn);
             if (!c->rm_split.count(key) && seen.insert(key).second) todo.push_back({emask, lostn});
         }
@@ -3930,7 +3728,7 @@ void rec_multi_precompile(te_clay *c, int rotated, const std::vector<RecMultiIte
 // same resident slices.  The programs go through the decode's device store and descriptor arena
 // (dec_image / dec_upload).  TE_ERR_UNSUPPORTED, before anything is enqueued: a stripe without a
 // program.  Caller holds c->mu, the handle's device current.
-int recover_multi_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const std::vector<RecMultiItem> &items,
+int recover_multi_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const std::vector<const RecItem *> &items,
                           uint8_t *d_out, hipStream_t s, te_recover_multi_stats &st_out) {
     const ClayHost &h = c->h;
     if (c->rm_cache.size() > c->dstore.max_cap) {
@@ -3942,7 +3740,8 @@ int recover_multi_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d
     std::unordered_map<uint64_t, uint32_t> pat_index;
     std::map<DecGroupKey, std::vector<RmSlots>> tabs;
     te_recover_multi_stats add{};
-    for (const RecMultiItem &m : items) {
+    for (const RecItem *p : items) {
+        const RecItem &m = *p;
         const DecItem &it = m.it;
         const uint64_t nlost = (uint64_t)__builtin_popcount(m.lost);
         const DecGroupKey gk{it.cs, it.slice_len};
@@ -4011,19 +3810,29 @@ int recover_multi_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d
     return TE_OK;
 }
 
-// The generic path: the existing decode into the object, the existing encode of all n slices, the
-// lost ones kept -- in windows of bounded workspace, as recover_batch's.  Caller holds c->mu.
-int recover_multi_generic(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, std::vector<RecMultiItem> &items,
-                          uint8_t *d_out, hipStream_t s) {
-    const uint64_t n = (uint64_t)c->h.n;
-    constexpr uint64_t kWinBlob = 1ull << 30, kWinSlices = 3ull << 30;
+// The generic path, for any lost mask: decode into the object, re-encode, keep the lost slices.
+// Per stripe a lost slice holds one shard (rotation): a data shard is a piece of the decoded object
+// (zero-padded like Slicer::encode's stripe, slicer.rs:276-283), so only the stripes with a parity
+// shard among the lost ones are re-encoded, writing those shards' chunks alone.  Objects go through
+// the device workspaces in windows (bounded memory).  Caller holds c->mu.
+int recover_generic(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const std::vector<const RecItem *> &items,
+                    uint8_t *d_out, hipStream_t s) {
+    const ClayHost &h = c->h;
+    const uint32_t n = (uint32_t)h.n;
+    const int rotated = cfg->rotated;
+    // windows: <= kWinBlob decoded bytes and <= kWinSlices re-encoded slice bytes
+    uint64_t kWinBlob = 1ull << 30, kWinSlices = 3ull << 30;
+    if (const char *e = tec_knob("TEC_RECOVER_WINDOW_BYTES")) {  // tests: force several windows
+        const uint64_t v = strtoull(e, nullptr, 10);
+        if (v) kWinBlob = kWinSlices = v;
+    }
     struct Win { size_t b, e; uint64_t blob, slices; };
     std::vector<Win> wins;
     uint64_t max_blob = 16, max_slices = 16;
     for (size_t i = 0; i < items.size();) {
         Win w{i, i, 0, 0};
         while (w.e < items.size()) {
-            const uint64_t bb = align16(items[w.e].it.blob_len), sb = n * items[w.e].it.slice_len;
+            const uint64_t bb = align16(items[w.e]->it.blob_len), sb = (uint64_t)n * items[w.e]->it.slice_len;
             if (w.e > w.b && (w.blob + bb > kWinBlob || w.slices + sb > kWinSlices)) break;
             w.blob += bb;
             w.slices += sb;
@@ -4042,36 +3851,64 @@ int recover_multi_generic(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d
     TE_HIP(c->rec_blob.ensure(max_blob));
     TE_HIP(c->rec_slices.ensure(max_slices));
     uint8_t *const blob = c->rec_blob.as<uint8_t>(), *const slices = c->rec_slices.as<uint8_t>();
+    // the keep filter of object m's stripe st: its parity shards among the lost slices, plus the
+    // column-0 parity chunks the LDS-DMA kernel reads back internally; 0 = all data, not encoded
+    const uint32_t col0_parity = ((1u << h.q) - 1u) & ~((1u << h.k) - 1u);
+    auto keep = [&](const RecItem &m, uint64_t st) {
+        uint32_t par = 0;
+        rec_each_lost(m.lost, [&](uint32_t sl, uint64_t) {
+            const uint32_t sh = slice_to_shard(rotated, n, (uint32_t)st, sl);
+            if (sh >= (uint32_t)h.k) par |= 1u << sh;
+        });
+        return par ? col0_parity | par : 0u;
+    };
+    std::vector<DecItem> dit;
+    std::vector<te_object> wenc;
+    std::vector<CopyJob> jobs;
+    std::vector<MetaJob> metas;
     int r = TE_OK;
     for (const Win &w : wins) {
-        std::vector<DecItem> dit;
-        std::vector<te_object> wenc;
+        dit.clear();
+        wenc.clear();
         uint64_t bo = 0, so = 0;
+        bool any_parity = false;
         for (size_t i = w.b; i < w.e; i++) {
-            DecItem it = items[i].it;
-            it.out_off = bo;
-            dit.push_back(it);
-            wenc.push_back(te_object{bo, it.blob_len, so, items[i].chunk_index});
-            bo += align16(it.blob_len);
-            so += n * it.slice_len;
+            const RecItem &m = *items[i];
+            dit.push_back(m.it);
+            dit.back().out_off = bo;
+            wenc.push_back(te_object{bo, m.it.blob_len, so, m.chunk_index});
+            bo += align16(m.it.blob_len);
+            so += (uint64_t)n * m.it.slice_len;
+            for (uint64_t st = 0; st < m.ns && !any_parity; st++) any_parity = keep(m, st) != 0;
         }
         if ((r = decode_enqueue(c, cfg, d_slices, dit.data(), dit.size(), blob, s, false))) break;
-        if ((r = encode_enqueue(c, cfg, blob, wenc.data(), wenc.size(), slices, s, false))) break;
-        std::vector<CopyJob> jobs;
-        std::vector<MetaJob> metas;
+        if (any_parity && (r = encode_enqueue(c, cfg, blob, wenc.data(), wenc.size(), slices, s, false, nullptr,
+                                              [&](size_t o, size_t st) { return keep(*items[w.b + o], st); })))
+            break;
+        // assemble the lost slices: per stripe the lost shard's chunk, then the suffix
+        jobs.clear();
+        metas.clear();
         for (size_t i = w.b; i < w.e; i++) {
-            const RecMultiItem &m = items[i];
-            const uint64_t slen = m.it.slice_len, body = m.ns * m.cs;
-            uint64_t j = 0;
-            for (uint32_t sl = 0; sl < (uint32_t)n; sl++) {
-                if (!((m.lost >> sl) & 1u)) continue;
-                uint8_t *dst = d_out + m.out_off + j++ * slen;
-                jobs.push_back(CopyJob{slices + wenc[i - w.b].out_off + (uint64_t)sl * slen, dst, body, body});
-                MetaJob mj{};
-                mj.dst = dst + body;
-                for (int k = 0; k < 6; k++) mj.words[k] = m.meta_w[k];
-                metas.push_back(mj);
-            }
+            const RecItem &m = *items[i];
+            const te_object &e = wenc[i - w.b];
+            const uint64_t cs = m.cs, slen = m.it.slice_len, len = m.it.blob_len;
+            rec_each_lost(m.lost, [&](uint32_t sl, uint64_t j) {
+                uint8_t *dst = d_out + m.out_off + j * slen;
+                for (uint64_t st = 0; st < m.ns; st++) {
+                    const uint32_t sh = slice_to_shard(rotated, n, (uint32_t)st, sl);
+                    if (sh >= (uint32_t)h.k) {
+                        jobs.push_back(CopyJob{slices + e.out_off + (uint64_t)sl * slen + st * cs, dst + st * cs, cs, cs});
+                    } else {
+                        // data shard sh of stripe st: object bytes [st*S + sh*cs, ...) clipped to the
+                        // stripe and the object, zero beyond
+                        const uint64_t start = st * m.stripe + (uint64_t)sh * cs;
+                        const uint64_t end = std::min<uint64_t>(len, (st + 1) * m.stripe);
+                        const uint64_t valid = start < end ? std::min<uint64_t>(cs, end - start) : 0;
+                        jobs.push_back(CopyJob{blob + e.data_off + std::min(start, len), dst + st * cs, cs, valid});
+                    }
+                }
+                metas.push_back(rec_meta(m, d_out, j));
+            });
         }
         if ((r = gather_meta_enqueue(c->rec, s, jobs, metas))) break;
     }
@@ -4079,90 +3916,106 @@ int recover_multi_generic(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d
     return r ? r : r2;
 }
 
-// locked = the caller holds the handle's lock (te_slicer_recover_multi, the host rebuild pipeline)
-// part = a window of a host call, as recover_batch's: the decode / encode launch stats go on summing
-// (c->rms is this window's alone; the pipeline sums it)
-int recover_multi_batch(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_multi_object *objs,
-                        const uint8_t *h_meta, size_t nobj, uint8_t *d_out, void *stream, bool locked, bool part = false) {
-    if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
+// Every recover call's device work: handle locked, its device current, the items validated.  The
+// items go by route (rec_route), each non-empty part in turn -- the class path, the multi-output
+// kernel, the generic path, which also takes the items of a part that answers TE_ERR_UNSUPPORTED
+// before it enqueues anything -- so one small object does not send a whole batch to the windowed
+// decode + re-encode.  The call's figures are added to `st`.
+int recover_enqueue(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const std::vector<RecItem> &items,
+                    uint8_t *d_out, hipStream_t s, te_recover_multi_stats &st) {
     const ClayHost &h = c->h;
-    std::vector<RecMultiItem> multi, generic;
-    std::vector<te_recover_object> single;  // one per lost slice of a single-path object
-    std::vector<uint8_t> single_meta;
-    te_recover_multi_stats st{};
-    for (size_t i = 0; i < nobj; i++) {
-        RecMultiItem m{};
-        const uint8_t *meta = h_meta + i * TE_META_SIZE;
-        if (int r = rec_multi_validate(c, objs[i], meta, m)) return r;
-        switch (rec_multi_route(h, (uint32_t)__builtin_popcount(m.lost), m.it.ns, m.it.cs, m.it.slice_len)) {
-            case kRecMultiKernel: multi.push_back(m); break;
-            case kRecMultiGeneric: generic.push_back(m); break;
-            default: {
-                uint64_t j = 0;
-                for (uint32_t sl = 0; sl < (uint32_t)h.n; sl++) {
-                    if (!((m.lost >> sl) & 1u)) continue;
-                    single.push_back(te_recover_object{objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask, sl,
-                                                       objs[i].out_off + j++ * objs[i].slice_len});
-                    single_meta.insert(single_meta.end(), meta, meta + TE_META_SIZE);
-                }
-                st.single_objects++;
-            }
+    std::vector<const RecItem *> part[3];
+    for (auto &p : part) p.reserve(items.size());
+    for (const RecItem &m : items)
+        part[rec_route(h, (uint32_t)__builtin_popcount(m.lost), m.it.ns, m.it.cs, m.it.slice_len)].push_back(&m);
+    std::vector<const RecItem *> &cls = part[kRecClass], &multi = part[kRecKernel], &generic = part[kRecGeneric];
+    // a part's metadata suffixes (and an empty blob's zero chunk), after its kernels
+    auto finish = [&](const std::vector<CopyJob> &zeros, const std::vector<MetaJob> &metas) {
+        if (c->rec_pending && c->rec_stream != s) TE_HIP(hipStreamWaitEvent(s, c->rec_done, 0));
+        const int r = gather_meta_enqueue(c->rec, s, zeros, metas), r2 = rec_mark_done(c, s);
+        return r ? r : r2;
+    };
+    if (!cls.empty()) {
+        // One staged decode whose program outputs only the lost node's chunk of every stripe,
+        // straight into the lost slice -- k slices read, 1 written, no decoded object and no
+        // re-encode (a lost parity node's C is produced by the same layered decode)
+        std::vector<DecItem> fi;
+        std::vector<CopyJob> zeros;
+        std::vector<MetaJob> metas;
+        fi.reserve(cls.size());
+        metas.reserve(cls.size());
+        for (const RecItem *m : cls)
+            rec_each_lost(m->lost, [&](uint32_t sl, uint64_t j) {
+                fi.push_back(m->it);
+                fi.back().lost = (int32_t)sl;
+                fi.back().out_off = m->out_off + j * m->it.slice_len;
+                if (m->it.ns == 0) zeros.push_back(CopyJob{d_out, d_out + fi.back().out_off, m->cs * m->ns, 0});
+                metas.push_back(rec_meta(*m, d_out, j));
+            });
+        int r = decode_enqueue(c, cfg, d_slices, fi.data(), fi.size(), d_out, s, false);
+        if (r == TE_ERR_UNSUPPORTED) {
+            generic.insert(generic.begin(), cls.begin(), cls.end());
+            cls.clear();
+        } else if (r || (r = finish(zeros, metas))) {
+            return r;
         }
     }
-    if (nobj == 0) return TE_OK;
-    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
-    std::unique_lock<std::mutex> lk(c->mu, std::defer_lock);
-    if (!locked) lk.lock();
-    if (!part) {
-        c->dls = te_decode_launch_stats{};
-        c->els = te_encode_launch_stats{};
-    }
-    c->rms = te_recover_multi_stats{};
-    if (!single.empty()) {  // the single-slice path, as it is: it takes the lock itself
-        if (!locked) lk.unlock();
-        const int r = recover_batch(c, cfg, d_slices, single.data(), single_meta.data(), single.size(), d_out, stream, true, locked);
-        if (r) return r;
-        if (!locked) lk.lock();
-    }
-    DeviceGuard dg(c->device);
-    TE_HIP(dg.err);
-    hipStream_t s = (hipStream_t)stream;
     if (!multi.empty()) {
-        const int r = recover_multi_enqueue(c, cfg, d_slices, multi, d_out, s, st);
+        std::vector<MetaJob> metas;
+        for (const RecItem *m : multi)
+            rec_each_lost(m->lost, [&](uint32_t, uint64_t j) { metas.push_back(rec_meta(*m, d_out, j)); });
+        int r = recover_multi_enqueue(c, cfg, d_slices, multi, d_out, s, st);
         if (r == TE_ERR_UNSUPPORTED) {
             generic.insert(generic.end(), multi.begin(), multi.end());
             multi.clear();
-        } else if (r) {
+        } else if (r || (r = finish({}, metas))) {
             return r;
         }
-        std::vector<MetaJob> metas;
-        for (const RecMultiItem &m : multi)
-            for (uint64_t j = 0; j < (uint64_t)__builtin_popcount(m.lost); j++) {
-                MetaJob mj{};
-                mj.dst = d_out + m.out_off + j * m.it.slice_len + m.ns * m.cs;
-                for (int k = 0; k < 6; k++) mj.words[k] = m.meta_w[k];
-                metas.push_back(mj);
-            }
-        if (!metas.empty()) {
-            if (c->rec_pending && c->rec_stream != s) TE_HIP(hipStreamWaitEvent(s, c->rec_done, 0));
-            const int rm = gather_meta_enqueue(c->rec, s, {}, metas), r2 = rec_mark_done(c, s);
-            if (rm || r2) return rm ? rm : r2;
-        }
     }
-    st.multi_objects = multi.size();
-    st.generic_objects = generic.size();
-    if (!generic.empty())
-        if (int r = recover_multi_generic(c, cfg, d_slices, generic, d_out, s)) return r;
-    c->rms = st;
-    return TE_OK;
+    st.single_objects += cls.size();
+    st.multi_objects += multi.size();
+    st.generic_objects += generic.size();
+    return generic.empty() ? (int)TE_OK : recover_generic(c, cfg, d_slices, generic, d_out, s);
 }
+
+// The device forms after their argument checks: the one lock of the call, its launch stats reset
+int recover_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const std::vector<RecItem> &items,
+                   uint8_t *d_out, void *stream) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->els = te_encode_launch_stats{};  // the keep-filter re-encode of the parity-lost stripes
+    c->rms = te_recover_multi_stats{};
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    return recover_enqueue(c, cfg, d_slices, items, d_out, (hipStream_t)stream, c->rms);
+}
+
 }  // namespace
 extern "C" {
+
+// The argument rule of the single-slice forms (rec_single); nothing is validated without a device
+int te_recover_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
+                            const te_recover_object *objs, const uint8_t *h_meta, size_t nobj, uint8_t *d_out,
+                            void *stream) {
+    if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
+    if (nobj == 0) return TE_OK;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::vector<RecItem> items(nobj);
+    for (size_t i = 0; i < nobj; i++)
+        if (int r = rec_validate(c, rec_single(c, objs[i]), h_meta + i * TE_META_SIZE, true, items[i])) return r;
+    return recover_device(c, cfg, d_slices, items, d_out, stream);
+}
 
 int te_recover_multi_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
                                   const te_recover_multi_object *objs, const uint8_t *h_meta, size_t nobj, uint8_t *d_out,
                                   void *stream) {
-    return recover_multi_batch(c, cfg, d_slices, objs, h_meta, nobj, d_out, stream, false);
+    if (!c || !cfg || (!objs && nobj) || (!h_meta && nobj)) return TE_ERR_INVALID_ARG;
+    std::vector<RecItem> items(nobj);
+    for (size_t i = 0; i < nobj; i++)
+        if (int r = rec_validate(c, objs[i], h_meta + i * TE_META_SIZE, false, items[i])) return r;
+    if (nobj == 0) return TE_OK;
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    return recover_device(c, cfg, d_slices, items, d_out, stream);
 }
 
 // Per call: the present slices go up once (upload_slices, the decode's staging), every lost slice
@@ -4182,15 +4035,18 @@ int te_slicer_recover_multi(te_clay *c, const te_slicer_cfg *cfg, const uint8_t 
     if (slice_len < TE_META_SIZE) return TE_ERR_INVALID_LAYOUT;
     const uint8_t *meta = slices[first] + slice_len - TE_META_SIZE;
     const te_recover_multi_object o{0, slice_len, avail, lost_mask, 0};
-    RecMultiItem m{};
-    if ((r = rec_multi_validate(c, o, meta, m))) return r;
+    std::vector<RecItem> m(1);
+    if ((r = rec_validate(c, o, meta, false, m[0]))) return r;
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
     std::lock_guard<std::mutex> lk(c->mu);
     DeviceGuard dg(c->device);
     TE_HIP(dg.err);
     if ((r = ensure_stream(c))) return r;
     if ((r = upload_slices(c, slices, slice_len, nlost * slice_len))) return r;
-    if ((r = recover_multi_batch(c, cfg, c->io_in.as<uint8_t>(), &o, meta, 1, c->io_out.as<uint8_t>(), c->stream, true))) return r;
+    c->dls = te_decode_launch_stats{};
+    c->els = te_encode_launch_stats{};
+    c->rms = te_recover_multi_stats{};
+    if ((r = recover_enqueue(c, cfg, c->io_in.as<uint8_t>(), m, c->io_out.as<uint8_t>(), c->stream, c->rms))) return r;
     for (size_t j = 0; j < nlost; j++)
         TE_HIP(hipMemcpyAsync(out[j], c->io_out.as<uint8_t>() + j * slice_len, slice_len, hipMemcpyDeviceToHost, c->stream));
     TE_HIP(hipStreamSynchronize(c->stream));
@@ -5159,137 +5015,106 @@ int te_decode_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const 
                                   (hipStream_t)stream);
 }
 
+}  // extern "C"
+namespace {
+// The verified recover forms' work after their own argument checks (`pre`: each object's outcome
+// on its present slices, `items` filled where that is TE_OK): the peers verified, the objects with
+// k verified peers rebuilt from those -- lost_mask stays what the caller asked for -- and one
+// launch over every rebuilt slice of every object; h_ok_mask[i] = the rebuilt slices that match.
+int recover_verified(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices, const te_recover_multi_object *objs,
+                     std::vector<RecItem> &items, const std::vector<int> &pre, const uint8_t *h_meta, const uint8_t *h_leaves,
+                     uint8_t *d_out, uint32_t *h_rejected_mask, uint32_t *h_ok_mask, int *h_status, hipStream_t s) {
+    const size_t nobj = items.size();
+    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
+    std::vector<te_verify_item> vi;
+    for (size_t i = 0; i < nobj; i++) {
+        h_ok_mask[i] = 0;
+        verify_push_slices(vi, i, n, objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask & all);
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->els = te_encode_launch_stats{};
+    c->rms = te_recover_multi_stats{};
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    std::vector<uint32_t> good(nobj);
+    int r = verify_wait(c, d_slices, vi, h_leaves, nobj * n, nobj, good.data(), s);
+    if (r) return r;
+    std::vector<RecItem> run;
+    std::vector<size_t> run_of;
+    for (size_t i = 0; i < nobj; i++) {
+        uint32_t ok;
+        if (resolve_survivors(c, objs[i].avail_mask & all, objs[i].slice_len, h_meta + i * TE_META_SIZE, pre[i], good[i],
+                              h_rejected_mask ? h_rejected_mask + i : nullptr, h_status + i, ok, items[i].it))
+            continue;
+        items[i].it.in_base = objs[i].slices_off;
+        run.push_back(items[i]);
+        run_of.push_back(i);
+    }
+    if (run.empty()) return TE_OK;
+    if ((r = recover_enqueue(c, cfg, d_slices, run, d_out, s, c->rms))) return r;
+    vi.clear();
+    for (size_t i : run_of)
+        rec_each_lost(objs[i].lost_mask, [&](uint32_t sl, uint64_t j) {
+            vi.push_back(te_verify_item{objs[i].out_off + j * objs[i].slice_len, objs[i].slice_len, (uint32_t)(i * n + sl),
+                                        (uint32_t)i, 1u << sl, 0});
+        });
+    if ((r = verify_wait(c, d_out, vi, h_leaves, nobj * n, nobj, good.data(), s))) return r;
+    for (size_t i : run_of) h_ok_mask[i] = good[i] & objs[i].lost_mask;
+    return TE_OK;
+}
+}  // namespace
+extern "C" {
+
+// The single form: its own argument rule (rec_single), and nothing validated without a device;
+// h_ok[i] is bit `lost` of the mask, as 0 or 1
 int te_recover_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
                                      const te_recover_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
                                      size_t nobj, uint8_t *d_out, uint32_t *h_rejected_mask, uint32_t *h_ok,
                                      int *h_status, void *stream) {
     if (!c || !cfg || ((!objs || !h_meta || !h_leaves || !h_status || !h_ok) && nobj)) return TE_ERR_INVALID_ARG;
-    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
+    const uint32_t n = (uint32_t)c->h.n;
     if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
     for (size_t i = 0; i < nobj; i++) {
         if (objs[i].slice_len % 4u || objs[i].slices_off % 4u || objs[i].out_off % 4u) return TE_ERR_INVALID_ARG;
         if (objs[i].lost >= n) return TE_ERR_INVALID_SLICE;
     }
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
-    std::vector<te_verify_item> vi;
+    std::vector<te_recover_multi_object> mo(nobj);
+    std::vector<RecItem> items(nobj);
+    std::vector<int> pre(nobj, TE_OK);
     for (size_t i = 0; i < nobj; i++) {
-        DecItem it{};
+        mo[i] = rec_single(c, objs[i]);
         // on the caller's unmasked avail_mask, as te_decode_verified_batch_device
-        const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, it);
+        const int r = rec_validate(c, mo[i], h_meta + i * TE_META_SIZE, true, items[i]);
         if (r && r != TE_ERR_NOT_ENOUGH_SLICES) return r;
-        h_status[i] = r;
+        h_status[i] = pre[i] = r;
         h_ok[i] = 0;
-        verify_push_slices(vi, i, n, objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask & all);
     }
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<uint32_t> good(nobj);
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        DeviceGuard dg(c->device);
-        TE_HIP(dg.err);
-        const int r = verify_wait(c, d_slices, vi, h_leaves, nobj * n, nobj, good.data(), s);
-        if (r) return r;
-    }
-    // the objects with k verified peers, rebuilt from those (the handle is locked by the call)
-    std::vector<te_recover_object> run;
-    std::vector<uint8_t> run_meta;
-    std::vector<size_t> run_of;
-    for (size_t i = 0; i < nobj; i++) {
-        uint32_t ok;
-        DecItem it{};
-        if (resolve_survivors(c, objs[i].avail_mask & all, objs[i].slice_len, h_meta + i * TE_META_SIZE, h_status[i], good[i],
-                              h_rejected_mask ? h_rejected_mask + i : nullptr, h_status + i, ok, it))
-            continue;
-        te_recover_object o = objs[i];
-        o.avail_mask = ok;
-        run.push_back(o);
-        run_meta.insert(run_meta.end(), h_meta + i * TE_META_SIZE, h_meta + (i + 1) * TE_META_SIZE);
-        run_of.push_back(i);
-    }
-    if (run.empty()) return TE_OK;
-    int r = recover_batch(c, cfg, d_slices, run.data(), run_meta.data(), run.size(), d_out, stream, false);
-    if (r) return r;
-    vi.clear();
-    for (size_t i : run_of)
-        vi.push_back(te_verify_item{objs[i].out_off, objs[i].slice_len, (uint32_t)(i * n + objs[i].lost), (uint32_t)i, 1u, 0});
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->device);
-    TE_HIP(dg.err);
-    if ((r = verify_wait(c, d_out, vi, h_leaves, nobj * n, nobj, good.data(), s))) return r;
-    for (size_t i : run_of) h_ok[i] = good[i] & 1u;
-    return TE_OK;
+    const int r = recover_verified(c, cfg, d_slices, mo.data(), items, pre, h_meta, h_leaves, d_out, h_rejected_mask, h_ok,
+                                   h_status, (hipStream_t)stream);
+    for (size_t i = 0; i < nobj; i++) h_ok[i] = (h_ok[i] >> objs[i].lost) & 1u;
+    return r;
 }
 
-// te_recover_verified_batch_device widened to a lost mask: the same two verify launches and waits,
-// recover_multi_batch between them, and one verify item per rebuilt slice (its object's mask gets
-// the slice's bit).  Every argument check comes before the call looks for a device.
+// The multi form: every argument check comes before the call looks for a device.
 int te_recover_multi_verified_batch_device(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *d_slices,
                                            const te_recover_multi_object *objs, const uint8_t *h_meta,
                                            const uint8_t *h_leaves, size_t nobj, uint8_t *d_out,
                                            uint32_t *h_rejected_mask, uint32_t *h_ok_mask, int *h_status, void *stream) {
     if (!c || !cfg || ((!objs || !h_meta || !h_leaves || !h_status || !h_ok_mask) && nobj)) return TE_ERR_INVALID_ARG;
-    const uint32_t n = (uint32_t)c->h.n, all = slice_bits(c);
-    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    if (nobj > 0xffffffffull / (uint32_t)c->h.n) return TE_ERR_INVALID_ARG;
+    std::vector<RecItem> items(nobj);
     std::vector<int> pre(nobj, TE_OK);
     for (size_t i = 0; i < nobj; i++) {
         if (objs[i].slice_len % 4u || objs[i].slices_off % 4u || objs[i].out_off % 4u) return TE_ERR_INVALID_ARG;
-        RecMultiItem m{};
-        const int r = rec_multi_validate(c, objs[i], h_meta + i * TE_META_SIZE, m);
+        const int r = rec_validate(c, objs[i], h_meta + i * TE_META_SIZE, false, items[i]);
         if (r && r != TE_ERR_NOT_ENOUGH_SLICES) return r;
         pre[i] = r;
     }
     if (device_count() <= 0) return TE_ERR_NO_DEVICE;
-    if (nobj == 0) return TE_OK;
-    std::vector<te_verify_item> vi;
-    for (size_t i = 0; i < nobj; i++) {
-        h_ok_mask[i] = 0;
-        verify_push_slices(vi, i, n, objs[i].slices_off, objs[i].slice_len, objs[i].avail_mask & all);
-    }
-    hipStream_t s = (hipStream_t)stream;
-    std::vector<uint32_t> good(nobj);
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        DeviceGuard dg(c->device);
-        TE_HIP(dg.err);
-        if (int r = verify_wait(c, d_slices, vi, h_leaves, nobj * n, nobj, good.data(), s)) return r;
-    }
-    // the objects with k verified peers, rebuilt from those; lost_mask stays what the caller asked for
-    std::vector<te_recover_multi_object> run;
-    std::vector<uint8_t> run_meta;
-    std::vector<size_t> run_of;
-    for (size_t i = 0; i < nobj; i++) {
-        uint32_t ok;
-        DecItem it{};
-        if (resolve_survivors(c, objs[i].avail_mask & all, objs[i].slice_len, h_meta + i * TE_META_SIZE, pre[i], good[i],
-                              h_rejected_mask ? h_rejected_mask + i : nullptr, h_status + i, ok, it))
-            continue;
-        te_recover_multi_object o = objs[i];
-        o.avail_mask = ok;
-        run.push_back(o);
-        run_meta.insert(run_meta.end(), h_meta + i * TE_META_SIZE, h_meta + (i + 1) * TE_META_SIZE);
-        run_of.push_back(i);
-    }
-    if (run.empty()) {
-        std::lock_guard<std::mutex> lk(c->mu);
-        c->rms = te_recover_multi_stats{};
-        return TE_OK;
-    }
-    int r = recover_multi_batch(c, cfg, d_slices, run.data(), run_meta.data(), run.size(), d_out, stream, false);
-    if (r) return r;
-    vi.clear();  // one launch over every rebuilt slice of every object
-    for (size_t i : run_of) {
-        uint64_t j = 0;
-        for (uint32_t sl = 0; sl < n; sl++)
-            if ((objs[i].lost_mask >> sl) & 1u)
-                vi.push_back(te_verify_item{objs[i].out_off + j++ * objs[i].slice_len, objs[i].slice_len, (uint32_t)(i * n + sl),
-                                            (uint32_t)i, 1u << sl, 0});
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    DeviceGuard dg(c->device);
-    TE_HIP(dg.err);
-    if ((r = verify_wait(c, d_out, vi, h_leaves, nobj * n, nobj, good.data(), s))) return r;
-    for (size_t i : run_of) h_ok_mask[i] = good[i] & objs[i].lost_mask;
-    return TE_OK;
+    return recover_verified(c, cfg, d_slices, objs, items, pre, h_meta, h_leaves, d_out, h_rejected_mask, h_ok_mask, h_status,
+                            (hipStream_t)stream);
 }
 
 int te_repair_verified_batch_device(te_clay *c, const uint8_t *d_helpers, const te_repair_object *objs,
@@ -6027,19 +5852,12 @@ int repair_object_bytes(const te_clay *c, const te_repair_object *objs, size_t n
     return TE_OK;
 }
 
-void recover_object_bytes(const te_clay *c, const te_recover_object *objs, size_t nobj, std::vector<uint64_t> &bytes) {
-    const uint32_t all = slice_bits(c);
-    bytes.resize(nobj);
-    for (size_t i = 0; i < nobj; i++)
-        bytes[i] = ((uint64_t)__builtin_popcount(objs[i].avail_mask & all) + 1u) * objs[i].slice_len;
-}
-
 // One window: nobj objects of the caller's arrays (already offset to the window's first object).
 struct RebuildWin {
-    const te_repair_object *rep = nullptr;   // repair window
-    const te_recover_object *rec = nullptr;  // recover window
-    const te_recover_multi_object *rm = nullptr;  // multi-slice recover window: L rebuilt slices per object, packed
-    te_recover_multi_stats *rms_sum = nullptr;    // ... its multi-kernel figures, summed over the call's windows
+    const te_repair_object *rep = nullptr;        // repair window
+    const te_recover_multi_object *rm = nullptr;  // recover window: L rebuilt slices per object, packed
+    RecItem *items = nullptr;                     // ... its objects as validated on their present slices
+    bool ok_flag = false;  // h_ok is 0 or 1 (a repair window, the single-slice recover form), not a mask of slices
     te_slicer_cfg cfg{};
     const uint8_t *h_in = nullptr, *h_meta = nullptr, *h_leaves = nullptr;  // h_leaves null: unverified
     uint8_t *h_out = nullptr;
@@ -6059,7 +5877,7 @@ struct RebuildWin {
     std::vector<uint32_t> good;                  // recover: the slices that go up / rebuild from
     std::vector<size_t> run;                     // the objects that rebuild
     std::vector<uint64_t> out_dev, out_len, out_host;  // per object: its rebuilt slice on the device / host
-    std::vector<uint32_t> lost;                  // the lost slice; a multi window: the lost mask
+    std::vector<uint32_t> lost;                  // repair: the lost slice; recover: the lost mask
     std::vector<uint32_t> avail;                 // recover: the caller's avail_mask and slice_len
     std::vector<uint64_t> slen;
     std::vector<CopyRun> hout;
@@ -6096,11 +5914,10 @@ void recover_resolve(const te_clay *c, RebuildWin &W) {
     W.hout.clear();
     W.out_sz = 0;
     for (size_t o = 0; o < W.nobj; o++) {
-        DecItem it{};
-        // h_rej is written only when leaves were given
+        // h_rej is written only when leaves were given; the object's item is now that of its survivors
         const int st = resolve_survivors(c, W.avail[o] & all, W.slen[o], W.h_meta + o * TE_META_SIZE,
                                          W.pre ? W.pre[o] : TE_OK, W.good[o], W.h_leaves && W.h_rej ? W.h_rej + o : nullptr,
-                                         W.h_status ? W.h_status + o : nullptr, W.good[o], it);
+                                         W.h_status ? W.h_status + o : nullptr, W.good[o], W.items[o].it);
         if (W.h_leaves && W.h_ok) W.h_ok[o] = 0;  // unverified: h_ok is not the call's to write
         if (st) continue;
         W.run.push_back(o);
@@ -6124,25 +5941,20 @@ int recover_stage_a(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
     W.slen.resize(W.nobj);
     bool dword = true;  // the recover kernels' and the rebuilt slice's verify item's alignment
     size_t results = 0;
-    auto fill = [&](size_t o, const auto &ob, uint32_t lost, uint64_t nlost) {
+    for (size_t o = 0; o < W.nobj; o++) {
+        const te_recover_multi_object &ob = W.rm[o];
+        const uint64_t nlost = (uint64_t)__builtin_popcount(ob.lost_mask);
         W.out_len[o] = nlost * ob.slice_len;
         W.out_host[o] = ob.out_off;
-        W.lost[o] = lost;
+        W.lost[o] = ob.lost_mask;
         W.avail[o] = ob.avail_mask;
         W.slen[o] = ob.slice_len;
         results += nlost;
         dword = dword && ob.slices_off % 4u == 0 && ob.out_off % 4u == 0;
-    };
-    for (size_t o = 0; o < W.nobj; o++) {
-        if (W.rm) fill(o, W.rm[o], W.rm[o].lost_mask, (uint64_t)__builtin_popcount(W.rm[o].lost_mask));
-        else fill(o, W.rec[o], W.rec[o].lost, 1);
     }
-    auto stage = [&](const auto *objs) {
-        return peer_stage_a(c, sl, s, W, objs, W.h_in, dword, results, c->rbs, &te_rebuild_launch_stats::pieces_uploaded,
-                            [&] { recover_resolve(c, W); },
-                            [&](const std::vector<CopyRun> &hin) { return rebuild_upload(c, sl, W, hin, s); });
-    };
-    return W.rm ? stage(W.rm) : stage(W.rec);
+    return peer_stage_a(c, sl, s, W, W.rm, W.h_in, dword, results, c->rbs, &te_rebuild_launch_stats::pieces_uploaded,
+                        [&] { recover_resolve(c, W); },
+                        [&](const std::vector<CopyRun> &hin) { return rebuild_upload(c, sl, W, hin, s); });
 }
 
 // Stage A of a repair window: the plan's fragments, packed (each 16-byte aligned, as
@@ -6196,6 +6008,15 @@ int repair_stage_a(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
     return ver_begin(sl.ver, sl.verh, W.vl, W.h_leaves, s);
 }
 
+// One call of f(slice, offset, length, bit) per rebuilt slice of the window's object o: the slice's
+// place in the object's output and the value its match adds to h_ok.  A repair window rebuilds
+// one slice per object (W.lost the slice, h_ok 0 or 1), a recover window its lost mask's, packed.
+template <class F>
+void rebuilt_slices(const RebuildWin &W, size_t o, F f) {
+    if (W.rep) return f(W.lost[o], 0, W.out_len[o], 1u);
+    rec_each_lost(W.lost[o], [&](uint32_t b, uint64_t j) { f(b, j * W.slen[o], W.slen[o], 1u << b); });
+}
+
 // Stage B (handle locked, its device current): the kernels, the rebuilt slices' hashes, the D2H copies.
 int rebuild_stage_b(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
     const uint32_t n = (uint32_t)c->h.n;
@@ -6218,37 +6039,22 @@ int rebuild_stage_b(te_clay *c, WinPipe &P, int k, RebuildWin &W) {
             for (size_t o = 0; o < W.nobj; o++)
                 items[o] = RepItem{W.rep[o].plan, W.frag_off.data() + o * n, W.out_dev[o], W.rep[o].metadata};
             if (int r = repair_enqueue(c, d_in, items.data(), items.size(), d_out, s)) return r;
-        } else if (W.rm) {  // the device form's routing (rec_multi_route), on the window's survivors
-            std::vector<te_recover_multi_object> objs;
-            std::vector<uint8_t> meta;
+        } else {  // the device form's routing (rec_route), on the window's survivors; the figures sum over the windows
+            std::vector<RecItem> run;
+            run.reserve(W.run.size());
             for (size_t o : W.run) {
-                objs.push_back(te_recover_multi_object{W.in_base[o], W.slen[o], W.good[o], W.lost[o], W.out_dev[o]});
-                meta.insert(meta.end(), W.h_meta + o * TE_META_SIZE, W.h_meta + (o + 1) * TE_META_SIZE);
+                run.push_back(W.items[o]);
+                run.back().it.in_base = W.in_base[o];
+                run.back().out_off = W.out_dev[o];
             }
-            if (int r = recover_multi_batch(c, &W.cfg, d_in, objs.data(), meta.data(), objs.size(), d_out, s, true, true)) return r;
-            rec_multi_stats_add(*W.rms_sum, c->rms);
-        } else {
-            std::vector<te_recover_object> objs;
-            std::vector<uint8_t> meta;
-            for (size_t o : W.run) {
-                objs.push_back(te_recover_object{W.in_base[o], W.rec[o].slice_len, W.good[o], W.rec[o].lost, W.out_dev[o]});
-                meta.insert(meta.end(), W.h_meta + o * TE_META_SIZE, W.h_meta + (o + 1) * TE_META_SIZE);
-            }
-            if (int r = recover_batch(c, &W.cfg, d_in, objs.data(), meta.data(), objs.size(), d_out, s, true, true)) return r;
+            if (int r = recover_enqueue(c, &W.cfg, d_in, run, d_out, s, c->rms)) return r;
         }
         if (W.device_hash) {
-            std::vector<te_verify_item> vi;
-            for (size_t o : W.run) {
-                if (!W.rm) {
-                    vi.push_back(te_verify_item{W.out_dev[o], W.out_len[o], (uint32_t)(o * n + W.lost[o]), (uint32_t)o, 1u, 0});
-                    continue;
-                }
-                uint64_t j = 0;  // the mask of object o gets the bit of each rebuilt slice that matches
-                for (uint32_t b = 0; b < n; b++)
-                    if ((W.lost[o] >> b) & 1u)
-                        vi.push_back(te_verify_item{W.out_dev[o] + j++ * W.slen[o], W.slen[o], (uint32_t)(o * n + b), (uint32_t)o,
-                                                    1u << b, 0});
-            }
+            std::vector<te_verify_item> vi;  // the mask of object o gets the bit of each rebuilt slice that matches
+            for (size_t o : W.run)
+                rebuilt_slices(W, o, [&](uint32_t b, uint64_t off, uint64_t len, uint32_t bit) {
+                    vi.push_back(te_verify_item{W.out_dev[o] + off, len, (uint32_t)(o * n + b), (uint32_t)o, bit, 0});
+                });
             if (int r = ver_masks(c, sl.ver, sl.verh, d_out, vi, W.vl, 1, s)) return r;
             st.slices_hashed_device += vi.size();
         }
@@ -6280,30 +6086,25 @@ int rebuild_stage_c(te_clay *c, WinPipe &P, int k, RebuildWin &W, bool last) {
     if (!verified) return TE_OK;
     if (W.device_hash) {
         const uint32_t *m = reinterpret_cast<const uint32_t *>(sl.verh.u8() + W.vl.h_mask(1));
-        for (size_t o : W.run) W.h_ok[o] = W.rm ? m[o] & W.lost[o] : m[o] & 1u;
+        for (size_t o : W.run) {
+            const uint32_t ok = m[o] & (W.rep ? 1u : W.lost[o]);
+            W.h_ok[o] = W.ok_flag ? ok != 0 : ok;
+        }
         return TE_OK;
     }
     const size_t n = (size_t)c->h.n;
     std::vector<HashItem> items;
     std::vector<std::pair<size_t, uint32_t>> who;  // the item's object and the value its match adds to h_ok
-    for (size_t o : W.run) {
-        if (!W.rm) {
-            items.push_back({W.h_out + W.out_host[o], W.out_len[o], W.h_leaves + (o * n + W.lost[o]) * TE_HASH_SIZE});
-            who.push_back({o, 1u});
-            continue;
-        }
-        uint64_t j = 0;
-        for (uint32_t b = 0; b < (uint32_t)n; b++)
-            if ((W.lost[o] >> b) & 1u) {
-                items.push_back({W.h_out + W.out_host[o] + j++ * W.slen[o], W.slen[o], W.h_leaves + (o * n + b) * TE_HASH_SIZE});
-                who.push_back({o, 1u << b});
-            }
-    }
+    for (size_t o : W.run)
+        rebuilt_slices(W, o, [&](uint32_t b, uint64_t off, uint64_t len, uint32_t bit) {
+            items.push_back({W.h_out + W.out_host[o] + off, len, W.h_leaves + (o * n + b) * TE_HASH_SIZE});
+            who.push_back({o, bit});
+        });
     std::vector<uint8_t> ok;
     hash_items_host(items, c->device, ok);
     for (size_t o : W.run) W.h_ok[o] = 0;  // a repair window's h_ok is first written here: whatever the caller left goes
     for (size_t j = 0; j < items.size(); j++)
-        if (ok[j]) W.h_ok[who[j].first] |= who[j].second;
+        if (ok[j]) W.h_ok[who[j].first] |= W.ok_flag ? 1u : who[j].second;
     st.slices_hashed_host += items.size();
     return TE_OK;
 }
@@ -6334,6 +6135,69 @@ bool rebuild_copy_only() {  // read per call: a benchmark switches it between le
     return co && co[0] == '1';
 }
 
+// te_recover_batch_host (single: rec_single's objects and argument rule) and
+// te_recover_multi_batch_host: every argument check, then the windows
+int recover_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_recover_multi_object *objs,
+                 const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *h_out, uint32_t *h_rejected_mask,
+                 uint32_t *h_ok_mask, int *h_status, size_t window_bytes, bool single) {
+    if (!c || !cfg || ((!objs || !h_meta || !h_slices || !h_out) && nobj)) return TE_ERR_INVALID_ARG;
+    const bool verified = h_leaves != nullptr;
+    if (verified && (!h_status || !h_ok_mask) && nobj) return TE_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)c->h.n;
+    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
+    std::vector<RecItem> items(nobj);
+    std::vector<int> pre(nobj, TE_OK);
+    std::vector<uint64_t> bytes(nobj);
+    for (size_t i = 0; i < nobj; i++) {
+        const int r = rec_validate(c, objs[i], h_meta + i * TE_META_SIZE, single, items[i]);
+        if (r && !(verified && r == TE_ERR_NOT_ENOUGH_SLICES)) return r;
+        pre[i] = r;
+        bytes[i] = rec_multi_object_bytes(c->h.n, objs[i].avail_mask, objs[i].lost_mask, objs[i].slice_len);
+    }
+    std::vector<size_t> cuts;
+    window_cuts(bytes, window_bytes, cuts);
+    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->dls = te_decode_launch_stats{};
+    c->els = te_encode_launch_stats{};
+    c->rbs = te_rebuild_launch_stats{};
+    c->rms = te_recover_multi_stats{};
+    if (nobj == 0) return TE_OK;
+    DeviceGuard dg(c->device);
+    TE_HIP(dg.err);
+    // h_slices is of one kind (header): asked of the first present slice, absent slots may be unmapped
+    bool pin_in = true;
+    for (size_t i = 0; i < nobj; i++)
+        if (const uint32_t m = objs[i].avail_mask & slice_bits(c)) {
+            pin_in = host_pinned(h_slices + objs[i].slices_off + (uint64_t)__builtin_ctz(m) * objs[i].slice_len);
+            break;
+        }
+    const bool pin_out = host_pinned(h_out), copy_only = rebuild_copy_only();
+    std::vector<RebuildWin> wins(cuts.size() - 1);
+    for (size_t w = 0; w < wins.size(); w++) {
+        RebuildWin &W = wins[w];
+        const size_t a = cuts[w];
+        W.rm = objs + a;
+        W.items = items.data() + a;
+        W.ok_flag = single;
+        W.cfg = *cfg;
+        W.h_in = h_slices;
+        W.h_out = h_out;
+        W.h_meta = h_meta + a * TE_META_SIZE;
+        W.h_leaves = verified ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
+        W.nobj = cuts[w + 1] - a;
+        W.h_rej = h_rejected_mask ? h_rejected_mask + a : nullptr;
+        W.h_ok = h_ok_mask ? h_ok_mask + a : nullptr;
+        W.h_status = h_status ? h_status + a : nullptr;
+        W.pre = pre.data() + a;
+        W.mode = g_commit_hashing.load();
+        W.pinned_in = pin_in;
+        W.pinned_out = pin_out;
+        W.copy_only = copy_only;
+    }
+    return rebuild_run(c, wins);
+}
+
 }  // namespace
 
 extern "C" {
@@ -6353,8 +6217,9 @@ int te_recover_window_plan(const te_clay *c, const te_recover_object *objs, size
                            size_t *cuts, size_t cap, size_t *nwindows) {
     if (!c || !nwindows || (!objs && nobj)) return TE_ERR_INVALID_ARG;
     *nwindows = 0;
-    std::vector<uint64_t> bytes;
-    recover_object_bytes(c, objs, nobj, bytes);
+    std::vector<uint64_t> bytes(nobj);  // rec_multi_object_bytes of one lost slice, whatever `lost` says
+    for (size_t i = 0; i < nobj; i++)
+        bytes[i] = ((uint64_t)__builtin_popcount(objs[i].avail_mask & slice_bits(c)) + 1u) * objs[i].slice_len;
     std::vector<size_t> v;
     window_cuts(bytes, window_bytes, v);
     return cuts_out(v, cuts, cap, nwindows);
@@ -6390,6 +6255,7 @@ int te_repair_batch_host(te_clay *c, const uint8_t *h_helpers, const te_repair_o
         RebuildWin &W = wins[w];
         const size_t a = cuts[w];
         W.rep = objs + a;
+        W.ok_flag = true;
         W.h_in = h_helpers;
         W.h_out = h_out;
         W.h_leaves = h_leaves ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
@@ -6403,67 +6269,17 @@ int te_repair_batch_host(te_clay *c, const uint8_t *h_helpers, const te_repair_o
     return rebuild_run(c, wins);
 }
 
+// The single form converts its objects at its boundary; its one lost slice makes h_ok 0 or 1 (ok_flag)
 int te_recover_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint8_t *h_slices, const te_recover_object *objs,
                           const uint8_t *h_meta, const uint8_t *h_leaves, size_t nobj, uint8_t *h_out,
                           uint32_t *h_rejected_mask, uint32_t *h_ok, int *h_status, size_t window_bytes) {
-    if (!c || !cfg || ((!objs || !h_meta || !h_slices || !h_out) && nobj)) return TE_ERR_INVALID_ARG;
-    const bool verified = h_leaves != nullptr;
-    if (verified && (!h_status || !h_ok) && nobj) return TE_ERR_INVALID_ARG;
-    const uint32_t n = (uint32_t)c->h.n;
-    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
-    std::vector<int> pre(nobj, TE_OK);
-    for (size_t i = 0; i < nobj; i++) {
-        if (objs[i].lost >= n) return TE_ERR_INVALID_SLICE;
-        DecItem it{};
-        const int r = decode_validate(c, h_meta + i * TE_META_SIZE, objs[i].slice_len, objs[i].avail_mask, it);
-        if (r && !(verified && r == TE_ERR_NOT_ENOUGH_SLICES)) return r;
-        pre[i] = r;
-        if (r) continue;
-        te_geometry g;
-        te_slicer_geometry(c, it.blob_len, &g);
-        if (g.slice_len != objs[i].slice_len) return TE_ERR_INVALID_LAYOUT;
+    std::vector<te_recover_multi_object> mo;
+    if (c && objs && nobj <= 0xffffffffull / (uint32_t)c->h.n) {  // (a larger count is recover_host's TE_ERR_INVALID_ARG)
+        mo.reserve(nobj);
+        for (size_t i = 0; i < nobj; i++) mo.push_back(rec_single(c, objs[i]));
     }
-    std::vector<uint64_t> bytes;
-    recover_object_bytes(c, objs, nobj, bytes);
-    std::vector<size_t> cuts;
-    window_cuts(bytes, window_bytes, cuts);
-    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->dls = te_decode_launch_stats{};
-    c->els = te_encode_launch_stats{};
-    c->rbs = te_rebuild_launch_stats{};
-    if (nobj == 0) return TE_OK;
-    DeviceGuard dg(c->device);
-    TE_HIP(dg.err);
-    // h_slices is of one kind (header): asked of the first present slice, absent slots may be unmapped
-    bool pin_in = true;
-    for (size_t i = 0; i < nobj; i++)
-        if (const uint32_t m = objs[i].avail_mask & slice_bits(c)) {
-            pin_in = host_pinned(h_slices + objs[i].slices_off + (uint64_t)__builtin_ctz(m) * objs[i].slice_len);
-            break;
-        }
-    const bool pin_out = host_pinned(h_out), copy_only = rebuild_copy_only();
-    std::vector<RebuildWin> wins(cuts.size() - 1);
-    for (size_t w = 0; w < wins.size(); w++) {
-        RebuildWin &W = wins[w];
-        const size_t a = cuts[w];
-        W.rec = objs + a;
-        W.cfg = *cfg;
-        W.h_in = h_slices;
-        W.h_out = h_out;
-        W.h_meta = h_meta + a * TE_META_SIZE;
-        W.h_leaves = verified ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
-        W.nobj = cuts[w + 1] - a;
-        W.h_rej = h_rejected_mask ? h_rejected_mask + a : nullptr;
-        W.h_ok = h_ok ? h_ok + a : nullptr;
-        W.h_status = h_status ? h_status + a : nullptr;
-        W.pre = pre.data() + a;
-        W.mode = g_commit_hashing.load();
-        W.pinned_in = pin_in;
-        W.pinned_out = pin_out;
-        W.copy_only = copy_only;
-    }
-    return rebuild_run(c, wins);
+    return recover_host(c, cfg, h_slices, objs ? mo.data() : nullptr, h_meta, h_leaves, nobj, h_out, h_rejected_mask, h_ok,
+                        h_status, window_bytes, true);
 }
 
 int te_recover_multi_window_plan(const te_clay *c, const te_recover_multi_object *objs, size_t nobj, size_t window_bytes,
@@ -6482,64 +6298,8 @@ int te_recover_multi_batch_host(te_clay *c, const te_slicer_cfg *cfg, const uint
                                 const te_recover_multi_object *objs, const uint8_t *h_meta, const uint8_t *h_leaves,
                                 size_t nobj, uint8_t *h_out, uint32_t *h_rejected_mask, uint32_t *h_ok_mask, int *h_status,
                                 size_t window_bytes) {
-    if (!c || !cfg || ((!objs || !h_meta || !h_slices || !h_out) && nobj)) return TE_ERR_INVALID_ARG;
-    const bool verified = h_leaves != nullptr;
-    if (verified && (!h_status || !h_ok_mask) && nobj) return TE_ERR_INVALID_ARG;
-    const uint32_t n = (uint32_t)c->h.n;
-    if (nobj > 0xffffffffull / n) return TE_ERR_INVALID_ARG;
-    std::vector<int> pre(nobj, TE_OK);
-    std::vector<uint64_t> bytes(nobj);
-    for (size_t i = 0; i < nobj; i++) {
-        RecMultiItem m{};
-        const int r = rec_multi_validate(c, objs[i], h_meta + i * TE_META_SIZE, m);
-        if (r && !(verified && r == TE_ERR_NOT_ENOUGH_SLICES)) return r;
-        pre[i] = r;
-        bytes[i] = rec_multi_object_bytes(c->h.n, objs[i].avail_mask, objs[i].lost_mask, objs[i].slice_len);
-    }
-    std::vector<size_t> cuts;
-    window_cuts(bytes, window_bytes, cuts);
-    if (device_count() <= 0) return TE_ERR_NO_DEVICE;
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->dls = te_decode_launch_stats{};
-    c->els = te_encode_launch_stats{};
-    c->rbs = te_rebuild_launch_stats{};
-    c->rms = te_recover_multi_stats{};
-    if (nobj == 0) return TE_OK;
-    DeviceGuard dg(c->device);
-    TE_HIP(dg.err);
-    // as te_recover_batch_host: h_slices is asked of the first present slice
-    bool pin_in = true;
-    for (size_t i = 0; i < nobj; i++)
-        if (const uint32_t m = objs[i].avail_mask & slice_bits(c)) {
-            pin_in = host_pinned(h_slices + objs[i].slices_off + (uint64_t)__builtin_ctz(m) * objs[i].slice_len);
-            break;
-        }
-    const bool pin_out = host_pinned(h_out), copy_only = rebuild_copy_only();
-    te_recover_multi_stats sum{};
-    std::vector<RebuildWin> wins(cuts.size() - 1);
-    for (size_t w = 0; w < wins.size(); w++) {
-        RebuildWin &W = wins[w];
-        const size_t a = cuts[w];
-        W.rm = objs + a;
-        W.rms_sum = &sum;
-        W.cfg = *cfg;
-        W.h_in = h_slices;
-        W.h_out = h_out;
-        W.h_meta = h_meta + a * TE_META_SIZE;
-        W.h_leaves = verified ? h_leaves + a * n * TE_HASH_SIZE : nullptr;
-        W.nobj = cuts[w + 1] - a;
-        W.h_rej = h_rejected_mask ? h_rejected_mask + a : nullptr;
-        W.h_ok = h_ok_mask ? h_ok_mask + a : nullptr;
-        W.h_status = h_status ? h_status + a : nullptr;
-        W.pre = pre.data() + a;
-        W.mode = g_commit_hashing.load();
-        W.pinned_in = pin_in;
-        W.pinned_out = pin_out;
-        W.copy_only = copy_only;
-    }
-    const int r = rebuild_run(c, wins);
-    c->rms = sum;
-    return r;
+    return recover_host(c, cfg, h_slices, objs, h_meta, h_leaves, nobj, h_out, h_rejected_mask, h_ok_mask, h_status,
+                        window_bytes, false);
 }
 
 int te_clay_rebuild_launch_stats(te_clay *c, te_rebuild_launch_stats *out) {

@@ -10,13 +10,14 @@
 namespace tec {
 
 // ---- routing: stated once, here ----
-// An object with fewer than kRecMultiMinLost lost slices runs the single-slice recover
-// (recover_batch: the class kernels, one call's launches per lost slice) -- a one-slice request is
-// today's request, launch for launch.  From kRecMultiMinLost on it runs the multi-output kernel
-// (recover_multi.hip) when the profile has plane programs (q = 10, t = 2, nu = 0) and the staged
-// kernels address its geometry (dec_geom_staged); any other object decodes on the existing decode
-// path and re-encodes (the generic path), keeping the lost slices.  An empty blob has nothing to
-// decode and takes the single path's metadata-only form whatever its lost count.
+// A lost index is a lost mask of one bit: every recover entry point routes its objects by rec_route.
+// An object with fewer than kRecMultiMinLost lost slices is a single-slice object (rec_multi_route):
+// a one-slice request through a multi entry point is the single entry point's request, launch for
+// launch.  From kRecMultiMinLost on it runs the multi-output kernel (recover_multi.hip) when the
+// profile has plane programs (q = 10, t = 2, nu = 0) and the staged kernels address its geometry
+// (dec_geom_staged); any other object decodes on the existing decode path and re-encodes (the
+// generic path), keeping the lost slices.  An empty blob has nothing to decode and is a
+// single-slice object whatever its lost count.
 // The threshold is 2, the smallest count the kernel exists for; scripts/recover_multi_bench.py
 // measures the crossover and DESIGN §4.13 records it.
 constexpr uint32_t kRecMultiMinLost = 2;
@@ -25,6 +26,30 @@ inline RecMultiPath rec_multi_route(const ClayHost &h, uint32_t nlost, uint64_t 
     if (nlost < kRecMultiMinLost || ns == 0) return kRecMultiSingle;
     const bool planes = h.q == kRepQ && h.t == 2 && h.nu == 0 && h.k >= 7 && h.k <= kDecMaxK;
     return planes && dec_geom_staged(h, cs, slice_len) ? kRecMultiKernel : kRecMultiGeneric;
+}
+// A single-slice object runs the class path (decode_enqueue with DecItem::lost: the staged decode
+// whose program outputs only the lost node's chunk, an item per lost slice) when the profile has
+// plane programs and the object is an empty blob (no stripe to decode: its one chunk is zeros) or
+// the staged kernels address its geometry; any other takes the generic path.  No bound on k here:
+// a profile the staged kernels do not compile for is decode_enqueue's TE_ERR_UNSUPPORTED, answered
+// before anything is enqueued, and its objects then take the generic path too.
+inline bool rec_single_class(const ClayHost &h, uint64_t ns, uint64_t cs, uint64_t slice_len) {
+    const bool planes = h.q == kRepQ && h.t == 2 && h.nu == 0;
+    return planes && (ns == 0 || dec_geom_staged(h, cs, slice_len));
+}
+// The route of one object: ns and cs as decode_validate gives them (an empty blob: ns = 0)
+enum RecPath { kRecClass = 0, kRecKernel = 1, kRecGeneric = 2 };
+inline RecPath rec_route(const ClayHost &h, uint32_t nlost, uint64_t ns, uint64_t cs, uint64_t slice_len) {
+    switch (rec_multi_route(h, nlost, ns, cs, slice_len)) {
+        case kRecMultiKernel: return kRecKernel;
+        case kRecMultiGeneric: return kRecGeneric;
+        default: return rec_single_class(h, ns, cs, slice_len) ? kRecClass : kRecGeneric;
+    }
+}
+// One call of f(slice, j) per lost slice of a mask, ascending: the j-th set bit is output slot j
+template <class F>
+inline void rec_each_lost(uint32_t lost, F f) {
+    for (uint64_t j = 0; lost; lost &= lost - 1u) f((uint32_t)__builtin_ctz(lost), j++);
 }
 
 // ---- arguments (te_recover_multi_object) ----

@@ -10,7 +10,9 @@
 //   split   for one survivor set per a0 and every lost-set size 1..13: the sub-masks partition
 //           the lost nodes, each compiles and fits (recover_multi_fits = decode_stage_fits of the
 //           direct-output kernel, and kDecMaxOut items a step), a set that fits whole is one part.
-//   args    rec_multi_check and rec_multi_route at their edges.
+//   args    rec_multi_check and rec_multi_route at their edges; rec_route, the route of every object:
+//           Clay(20,7,16) and Clay(12,8,11), one and several lost slices, an empty blob, staged and
+//           unstaged geometries.
 // Exit status = number of failed checks.
 #include <cstdio>
 #include <cstdlib>
@@ -285,6 +287,52 @@ int main() {
     ClayHost h2;
     if (h2.init(14, 10, 13) != 0) return 2;
     CHECK(rec_multi_route(h2, 2, 1, 25600, 25648) == kRecMultiGeneric);  // no plane programs
+
+    // ---- the route of every object (rec_route): a lost index is a lost mask of one bit ----
+    // Clay(20,7,16), chunk sizes by the oracle's rule.  A staged geometry: one slice the class path,
+    // several the multi-output kernel.
+    CHECK(rec_route(H, 1, 3, 3000, 9048) == kRecClass);
+    CHECK(rec_route(H, 2, 3, 3000, 9048) == kRecKernel);
+    CHECK(rec_route(H, 13, 3, 3000, 9048) == kRecKernel);
+    // an unstaged one (999 bytes: sub-chunks of 2 bytes): the generic path whatever the count
+    const size_t cs999 = oc_chunk_size_for(oc.data(), 999);
+    CHECK(cs999 == 200 && !dec_geom_staged(H, cs999, cs999 + 48));
+    CHECK(rec_route(H, 1, 1, cs999, cs999 + 48) == kRecGeneric);
+    CHECK(rec_route(H, 2, 1, cs999, cs999 + 48) == kRecGeneric);
+    // every length below the first staged one is unstaged: chunks come in steps of 200 bytes per 1,400
+    // of the object, so 4,201 bytes are the first with sub-chunks of 8
+    size_t first_staged = 0;
+    for (size_t ln = 1; ln <= 6000 && !first_staged; ln++) {
+        const size_t c1 = oc_chunk_size_for(oc.data(), ln);
+        if (dec_geom_staged(H, c1, c1 + 48)) first_staged = ln;
+        else CHECK(rec_route(H, 1, 1, c1, c1 + 48) == kRecGeneric && rec_route(H, 3, 1, c1, c1 + 48) == kRecGeneric);
+    }
+    CHECK(first_staged == 4201 && rec_route(H, 1, 1, 800, 848) == kRecClass);
+    // an empty blob (ns = 0): nothing to decode, the class path's zero chunk whatever the count
+    CHECK(rec_route(H, 1, 0, 0, 248) == kRecClass && rec_route(H, 13, 0, 0, 248) == kRecClass);
+    CHECK(rec_single_class(H, 0, 0, 248) && rec_single_class(H, 1, 800, 848) && !rec_single_class(H, 1, 700, 748));
+    // a slice range past the 31-bit offsets is unstaged as well
+    CHECK(rec_route(H, 1, 1, 110000000, 110000048) == kRecGeneric && rec_route(H, 2, 1, 110000000, 110000048) == kRecGeneric);
+    // Clay(12,8,11) has no plane programs: the generic path, an empty blob included
+    ClayHost h3;
+    if (h3.init(12, 8, 11) != 0) return 2;
+    std::vector<uint8_t> oc3((size_t)oc_clay_sizeof());
+    oc_clay_init(oc3.data(), 12, 8, 11);
+    const size_t cs3 = oc_chunk_size_for(oc3.data(), 250001);
+    CHECK(cs3 % (size_t)h3.alpha == 0 && dec_geom_staged(h3, cs3, cs3 + 48));  // the geometry is not what rules it out
+    for (uint32_t nl : {1u, 2u, 4u}) {
+        CHECK(rec_route(h3, nl, 1, cs3, cs3 + 48) == kRecGeneric);
+        CHECK(rec_route(h3, nl, 1, (size_t)h3.alpha, (size_t)h3.alpha + 48) == kRecGeneric);  // unstaged too
+        CHECK(rec_route(h3, nl, 0, 0, (size_t)h3.alpha + 48) == kRecGeneric);
+    }
+    CHECK(!rec_single_class(h3, 0, 0, 248) && !rec_single_class(h2, 1, 25600, 25648));
+    // rec_each_lost: ascending slices, the j-th set bit is output slot j
+    {
+        std::vector<uint32_t> got;
+        rec_each_lost(0x80025u, [&](uint32_t sl, uint64_t j) { CHECK(j == got.size()); got.push_back(sl); });
+        CHECK((got == std::vector<uint32_t>{0, 2, 5, 19}));
+        rec_each_lost(0u, [&](uint32_t, uint64_t) { CHECK(!"no lost slice"); });
+    }
 
     printf("rec_multi pairs %ld passes %ld split %ld rows %ld split_sets %ld (split %ld whole %ld) bad %d\n", pairs, passes,
            nsplit, rows_total, split_sets, split_found, whole_found, bad);
