@@ -12,7 +12,14 @@
 //           direct-output kernel, and kDecMaxOut items a step), a set that fits whole is one part.
 //   args    rec_multi_check and rec_multi_route at their edges; rec_route, the route of every object:
 //           Clay(20,7,16) and Clay(12,8,11), one and several lost slices, an empty blob, staged and
-//           unstaged geometries.
+//           unstaged geometries; Clay(20,8,17), (20,9,18), (20,10,19): the kernel from two lost slices
+//           on at a staged geometry, the generic path below 8-byte sub-chunks, one lost the class path.
+// Run with no argument it is Clay(20,7,16), all three parts.  `<k>` (8, 9 or 10; 7 too) runs the
+// values and split parts and the rec_route edges of Clay(20,k,k+9): a0 from max(0, k - 10) to
+// min(k, 10), lost sets of 2, 3, ceil((n - k) / 2) and n - k slices.  `report k:avail:lost:rot:st ...`
+// (masks in hex, by slice) prints what the engine builds for each named case -- the passes of the
+// stripe and per pass nslots, nscratch, max_out, the LDS rows, the finish steps that store both rows
+// of a pair and those that store one -- for tests/test_recover_multi_geometry_cases.py.
 // Exit status = number of failed checks.
 #include <cstdio>
 #include <cstdlib>
@@ -38,12 +45,24 @@ static int bad = 0;
         }                                                          \
     } while (0)
 
-static constexpr int N = 20, K = 7;
+static constexpr int N = 20;
+static int K = 7;  // the profile: Clay(20, K, K + 9)
 static ClayHost H;
 
 static uint8_t mul4(const uint32_t t[4], uint8_t x) {  // PermTab4 product, one byte
     uint8_t r = 0;
     for (int f = 0; f < 4; f++) r ^= (uint8_t)(t[f] >> (8 * ((x >> (2 * f)) & 3)));
+    return r;
+}
+static uint8_t mul5(const PermTab &t, uint8_t x) {  // PermTab product (fields of 3, 3 and 2 bits), one byte
+    auto at = [&](int w0, uint32_t j) { return (uint8_t)(t.t[w0 + (j >> 2)] >> (8 * (j & 3))); };
+    return (uint8_t)(at(0, x & 7u) ^ at(2, (x >> 3) & 7u) ^ at(4, x >> 6));
+}
+// The pattern's matrix entry times x: the tables the kernel reads (D), and where the pattern has
+// them (13 x 7: Clay(20,7,16)) the class kernels' D4, which must agree
+static uint8_t mulD(const GpePattern &P, int e, int j, uint8_t x) {
+    const uint8_t r = mul5(P.D[e][j], x);
+    if (P.nerased <= (uint32_t)kClsMaxE && P.nknown <= (uint32_t)kClsMaxK) CHECK(mul4(P.D4[e][j], x) == r);
     return r;
 }
 static uint8_t pft3(uint8_t a, uint8_t b) { return (uint8_t)(a ^ gf_mul(2, (uint8_t)(a ^ b))); }
@@ -104,7 +123,7 @@ static void run(const GpePattern &P, const std::vector<DecStep> &steps, const ui
             for (int e = 0; e < NE; e++) {
                 if (S.ek[e] == kErSkip) continue;
                 uint8_t a = 0;
-                for (int j = 0; j < NK; j++) a ^= mul4(P.D4[e][j], u[j]);
+                for (int j = 0; j < NK; j++) a ^= mulD(P, e, j, u[j]);
                 switch (S.ek[e]) {
                     case kErRed: put(S.ed0[e], a); break;
                     case kErType1: {
@@ -155,11 +174,77 @@ static void check_split(const GpePattern &P, uint64_t lost, const std::vector<ui
     nsplit += subs.size() > 1;
 }
 
-int main() {
-    if (H.init(N, K, 16) != 0) return 2;
+// rec_route of Clay(20,k,k+9), k = 8..10 (the profiles the class kernels do not serve, with plane
+// programs all the same): two or more lost slices are the multi-output kernel at a staged geometry
+// and the generic path below sub-chunks of 8 bytes; one lost slice is the class path (decode_enqueue
+// with DecItem::lost), an empty blob included.
+static void route_edges(int k) {
+    ClayHost h;
+    if (h.init(N, k, k + 9) != 0) {
+        CHECK(!"profile");
+        return;
+    }
+    for (uint32_t nl = 2; nl <= (uint32_t)(N - k); nl++) {
+        CHECK(rec_route(h, nl, 1, 800, 848) == kRecKernel && rec_multi_route(h, nl, 1, 800, 848) == kRecMultiKernel);
+        CHECK(rec_route(h, nl, 3, 14400, 3 * 14400 + 48) == kRecKernel);
+        CHECK(rec_route(h, nl, 1, 600, 648) == kRecGeneric);  // sub-chunks of 6 bytes
+        CHECK(rec_route(h, nl, 1, 200, 248) == kRecGeneric);
+        CHECK(rec_route(h, nl, 0, 0, 248) == kRecClass);  // an empty blob
+        CHECK(rec_route(h, nl, 1, 110000000, 110000048) == kRecGeneric);  // past the 31-bit offsets
+    }
+    CHECK(rec_route(h, 1, 1, 800, 848) == kRecClass && rec_multi_route(h, 1, 1, 800, 848) == kRecMultiSingle);
+    CHECK(rec_route(h, 1, 1, 600, 648) == kRecGeneric && rec_route(h, 1, 0, 0, 248) == kRecClass);
+    CHECK(rec_single_class(h, 1, 800, 848) && !rec_single_class(h, 1, 700, 748));
+}
+
+// One line per case and per pass of it, as the engine builds them (recover_multi_enqueue: the
+// stripe's padded erasure mask and lost nodes, rec_multi_split, a job and a slot table per part)
+static int report(int argc, char **argv) {
+    for (int i = 2; i < argc; i++) {
+        unsigned k = 0, avail = 0, lost = 0, rot = 0, st = 0;
+        if (sscanf(argv[i], "%u:%x:%x:%u:%u", &k, &avail, &lost, &rot, &st) != 5 || k < 7 || k > 10) return 2;
+        ClayHost h;
+        if (h.init(N, (int)k, (int)k + 9) != 0) return 2;
+        if (rec_multi_check(N, (int)k, avail, lost) != TE_OK || __builtin_popcount(avail) < (int)k) return 2;
+        const uint64_t emask = stripe_emask(h, (int)rot, avail, st), lostn = rec_multi_lost_nodes(h, (int)rot, lost, st);
+        GpePattern P;
+        std::vector<uint16_t> pool;
+        if (!h.gpe_pattern(emask, P, pool)) return 2;
+        const std::vector<uint64_t> subs = rec_multi_split(h, P, lostn);
+        printf("case %s passes %zu emask %05llx lostn %05llx\n", argv[i], subs.size(), (unsigned long long)emask,
+               (unsigned long long)lostn);
+        for (uint64_t sub : subs) {
+            RecMultiProg R;
+            std::vector<DecStep> raw;
+            if (!rec_multi_compile(h, P, sub, R, &raw)) return 2;
+            const RmSlots tab = rec_multi_slots(h, (int)rot, lost, sub, st);
+            int noslot = 0, both = 0, one = 0;
+            for (int node = 0; node < N; node++) noslot += ((lostn >> node) & 1ull) && tab.slot[node] == kRmNoSlot;
+            for (const DecStep &S : raw)
+                for (uint32_t e = 0; e < P.nerased; e++)
+                    if (S.ek[e] == kErFinish) {
+                        const int stored = (S.ed0[e] != kLocNone) + (S.epd[e] != kLocNone);
+                        both += stored == 2;
+                        one += stored == 1;
+                    }
+            printf("pass sub %05llx nslots %u nscratch %u max_out %u rows %u noslot %d finish_both %d finish_one %d\n",
+                   (unsigned long long)sub, R.H.nslots, R.H.nscratch, R.H.max_out, recover_multi_rows(R.H.nslots), noslot, both,
+                   one);
+        }
+    }
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "report")) return report(argc, argv);
+    const bool full = argc < 2;  // no argument: Clay(20,7,16), every part, as before the profile argument
+    if (!full) K = atoi(argv[1]);
+    if (K < 7 || K > 10) return 2;
+    const int E = N - K, a0_min = K > 10 ? K - 10 : 0, a0_max = K < 10 ? K : 10;
+    if (H.init(N, K, K + 9) != 0) return 2;
     std::vector<uint8_t> oc((size_t)oc_clay_sizeof());
-    oc_clay_init(oc.data(), N, K, 16);
-    const size_t len = 2800;  // sc = 2 bytes: chunk 200 B
+    oc_clay_init(oc.data(), N, K, K + 9);
+    const size_t len = (size_t)400 * K;  // sc = 2 bytes: chunk 200 B
     const size_t cs = oc_chunk_size_for(oc.data(), len), sc = cs / 100;
     std::vector<uint8_t> data(len), chunks(N * cs);
     std::mt19937_64 rng(0x726d756c7469ull);
@@ -170,8 +255,8 @@ int main() {
     // ---- values ----
     long pairs = 0, passes = 0, nsplit = 0, rows_total = 0;
     bool col_only[2] = {false, false}, col_both = false, rot_seen[2] = {false, false};
-    const int sizes[4] = {2, 3, 7, 13};
-    for (int a0 = 0; a0 <= 7; a0++)
+    const int sizes[4] = {2, 3, (E + 1) / 2, E};  // Clay(20,7,16): 2, 3, 7, 13
+    for (int a0 = a0_min; a0 <= a0_max; a0++)
         for (int size : sizes)
             for (int rep = 0; rep < 16; rep++) {
                 const int rotated = (int)(rng() % 2);
@@ -202,8 +287,9 @@ int main() {
                 if (!H.gpe_pattern(emask, P, pool)) return 2;
                 const std::vector<uint64_t> subs = rec_multi_split(H, P, lostn);
                 check_split(P, lostn, subs, nsplit);
-                // all 13 erased nodes never fit one pass (tests/test_gpu_recover_multi.py's split case relies on it)
-                CHECK(size != 13 || subs.size() >= 2);
+                // all n - k erased nodes never fit one pass (tests/test_gpu_recover_multi.py's split case and
+                // tests/recover_multi_geometry_cases.py's rely on it)
+                CHECK(size != E || subs.size() >= 2);
                 std::vector<uint8_t> out((size_t)size * cs, 0xEE);
                 std::vector<int> written((size_t)size * cs, 0);
                 long rows = 0;
@@ -231,10 +317,10 @@ int main() {
                 rows_total += rows;
                 pairs++;
             }
-    CHECK(pairs >= 500 && col_only[0] && col_only[1] && col_both && rot_seen[0] && rot_seen[1]);
+    CHECK(pairs == 64 * (a0_max - a0_min + 1) && col_only[0] && col_only[1] && col_both && rot_seen[0] && rot_seen[1]);
     // the check can fail: a table that sends a node to another slot must not reproduce the slices
     {
-        const uint64_t emask = 0xfffffull & ~0x0c07cull;
+        const uint64_t emask = 0xfffffull & ~(K == 7 ? 0x0c07cull : ((1ull << K) - 1ull) << 2);  // nodes 0 and 1 erased
         GpePattern P;
         pool.clear();
         if (!H.gpe_pattern(emask, P, pool)) return 2;
@@ -253,13 +339,13 @@ int main() {
 
     // ---- split rule: one survivor set per a0, every lost-set size ----
     long split_sets = 0, split_found = 0, whole_found = 0;
-    for (int a0 = 0; a0 <= 7; a0++) {
+    for (int a0 = a0_min; a0 <= a0_max; a0++) {
         const uint32_t surv = survivors(rng, a0), er = ((1u << N) - 1u) & ~surv;
         GpePattern P;
         pool.clear();
         if (!H.gpe_pattern(er, P, pool)) return 2;
-        for (int size = 1; size <= 13; size++)
-            for (int rep = 0; rep < (size == 13 ? 1 : 24); rep++) {
+        for (int size = 1; size <= E; size++)
+            for (int rep = 0; rep < (size == E ? 1 : 24); rep++) {
                 const uint64_t lostn = pick(rng, er, size);
                 long ns = 0;
                 check_split(P, lostn, rec_multi_split(H, P, lostn), ns);
@@ -270,7 +356,15 @@ int main() {
     }
     CHECK(split_found > 0 && whole_found > 0);  // both outcomes are exercised
 
+    if (!full) {
+        route_edges(K);
+        printf("rec_multi k %d pairs %ld passes %ld split %ld rows %ld split_sets %ld (split %ld whole %ld) bad %d\n", K, pairs,
+               passes, nsplit, rows_total, split_sets, split_found, whole_found, bad);
+        return bad > 255 ? 255 : bad;
+    }
+
     // ---- arguments and routing ----
+    for (int k = 8; k <= 10; k++) route_edges(k);
     CHECK(rec_multi_check(N, K, 0x7f, 0) == TE_ERR_INVALID_ARG);
     CHECK(rec_multi_check(N, K, 0x7f, 1u << 20) == TE_ERR_INVALID_ARG);
     CHECK(rec_multi_check(N, K, 0x7f, 0x40) == TE_ERR_INVALID_ARG);

@@ -1,32 +1,59 @@
 """The multi-output rebuild's host side, checked on the host (no GPU):
-tests/native/rec_multi_check.cpp runs tape_amd/csrc/rec_multi_plan.hpp for Clay(20,7,16) -- 512
+tests/native/rec_multi_check.cpp (built once) runs tape_amd/csrc/rec_multi_plan.hpp for Clay(20,7,16) -- 512
 seeded (survivor set, lost subset) pairs over every a0 = 0..7, lost sets of 2, 3, 7 and 13 slices
 in either column and across both, identity and rotated layouts: each sub-mask's program interpreted
 value by value, every output row through the job's node -> slot table, must rebuild exactly the lost
 slices' chunks of an oracle-encoded stripe; the split rule over every lost-set size for one
 survivor set per a0 (a partition, every part compiles and fits, a set that fits whole stays whole);
-the mask rules and the routing rule at their edges.  Then the argument errors through the C ABI."""
+the mask rules and the routing rule at their edges.  The same values and split parts run for
+Clay(20,8,17), (20,9,18) and (20,10,19) (`rec_multi_check <k>`), whose programs have other matrix
+tables, 12, 11 and 10 padded erasures and slot tables of their own; its report mode is what
+tests/test_recover_multi_geometry_cases.py reads.  Then the argument errors through the C ABI."""
 import ctypes as C
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import rec_multi_native as native
 
 
-def test_rec_multi_plan(tmp_path):
-    exe = str(tmp_path / "rec_multi_check")
-    ora = os.path.join(ROOT, "oracle")
-    if not os.path.exists(os.path.join(ora, "libclay_oracle.so")):
-        subprocess.run(["make", "-s", "-C", ora], check=True)
-    r = subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++20", "-Wall", "-I", os.path.join(ROOT, "tape_amd", "csrc"),
-                        os.path.join(ROOT, "tests", "native", "rec_multi_check.cpp"), "-L", ora, "-lclay_oracle",
-                        "-Wl,-rpath," + ora, "-o", exe], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+@pytest.fixture(scope="module")
+def check_exe(tmp_path_factory):
+    """tests/native/rec_multi_check.cpp, built once for every run of the session."""
+    return native.build(tmp_path_factory)
+
+
+def test_rec_multi_plan(check_exe):
+    r = subprocess.run([check_exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]  # the exit status is the number of failed checks
     assert "rec_multi pairs 512" in r.stdout and r.stdout.rstrip().endswith("bad 0")
+    assert r.stdout.rstrip() == ("rec_multi pairs 512 passes 758 split 198 rows 320000 split_sets 2312 "
+                                 "(split 1081 whole 1231) bad 0")  # the run is seeded: the line as it has always been
+
+
+@pytest.mark.parametrize("k", [8, 9, 10])
+def test_rec_multi_plan_other_profiles(check_exe, k):
+    """Clay(20,k,k+9): the values and split parts and the rec_route edges.  64 pairs per a0 (16 of
+    each lost-set size), a0 = 0..min(k, 10); a run takes about two seconds."""
+    r = subprocess.run([check_exe, str(k)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    a0s = min(k, 10) - max(0, k - 10) + 1
+    assert f"rec_multi k {k} pairs {64 * a0s} " in r.stdout and r.stdout.rstrip().endswith("bad 0")
+    # every pair stores alpha rows per lost slice exactly once: 16 pairs of 2, 3, ceil(m / 2) and m slices per a0
+    m = 20 - k
+    assert f" rows {a0s * 16 * (2 + 3 + (m + 1) // 2 + m) * 100} " in r.stdout
+
+
+def test_rec_multi_report(check_exe):
+    """The report mode on a case whose figures are known: two lost nodes of column 0 of
+    Clay(20,7,16) are one pass, a pair that is finished together; a malformed case is refused."""
+    r = subprocess.run([check_exe, "report", "7:3c0d:12:0:0"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = r.stdout.splitlines()
+    assert lines[0].split()[:4] == ["case", "7:3c0d:12:0:0", "passes", "1"] and len(lines) == 2
+    f = dict(zip(lines[1].split()[1::2], lines[1].split()[2::2]))
+    assert f["sub"] == "00012" and int(f["rows"]) == int(f["nslots"]) + 2 and int(f["finish_both"]) > 0 and f["noslot"] == "0"
+    assert subprocess.run([check_exe, "report", "7:3c0d:1:0:0"], capture_output=True).returncode == 2  # slice 0 is present
 
 
 # ---- argument validation through the C ABI: every error below is decided before any device use ----
